@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the MI355X Ed25519 verify engine (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c5] [--n PER_GPU]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c5] [--n PER_GPU] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,7 +24,14 @@ over ranks of the timed region.  N > 1 adds two sub-lines (BASELINE.json configs
 Default workload (N=1): BASELINE config C2 — 1,000,000 single-signer Ed25519 signatures over
 300-byte messages, distinct key per signature, generated on the GPU by the engine's signer.
 
-Extra fields on the JSON line:
+A plain run sets up the batch, warms up, times the K steps and prints the headline line (metric, value, unit,
+ms_per_step, config); nothing else is measured.  `--dump-outputs DIR` then also writes what the last timed step
+returned to its caller, as float32: DIR/verdicts.npy, one 0/1 value per signature of the verdict bitmap (N > 1: of
+the gathered bitmap); with --config c3 DIR/tx_ok.npy and DIR/tx_ids.npy (the recomputed id bytes).  Keys, messages
+and signatures come from fixed seeds, so the same arguments give the same inputs in every run.
+
+Extra fields on the JSON line with `--full` (every leg below runs after the timed steps and only then; the N > 1
+sub-lines above too):
   roofline      VALU-issue roofline of the dominant kernel (cv_hs_straus_kernel: 130,460 32x32->64
                 MACs per verify) against the measured v_mad_u64_u32
                 peak of this GPU, kernel time from HIP events on whole-chunk launches of the same
@@ -727,10 +734,13 @@ def straus_roofline(eng, local: int, n: int, straus_ms: float, kern_ms: float, m
             "group": {"kernel_ms": kern_ms, "achieved": group / 1e12, "frac": group / mad_rate}}
 
 
-def run_c3(eng, local, rank, world, sh, dev, ntx: int, steps: int, warmup: int):
+def run_c3(eng, local, rank, world, sh, dev, ntx: int, steps: int, warmup: int, phases: bool = True,
+           keep_outputs: bool = False):
     """C3 step (BASELINE.json configs[2]): recompute every tx id (leaf SHA-256 + Merkle tree), verify
     all signatures over the claimed ids, then per transaction: id matches AND all its signature bits
-    set.  Returns the timing dict (rank 0's view after the max over ranks)."""
+    set.  Returns the timing dict (rank 0's view after the max over ranks).  phases: also time the Merkle
+    call and the verify kernels one by one, in launches of their own after the timed steps.  keep_outputs:
+    the last timed step's per-transaction verdicts and recomputed ids, as host arrays under "outputs"."""
     t0 = time.perf_counter()
     tb = workload.make_tx_batch(eng, local, ntx, 8, seed=20261015 + 7919 * rank, stream=sh)
     log(f"[rank {rank}] generated {ntx} txs / {tb.sigs.n} signatures on GPU in {time.perf_counter() - t0:.2f}s")
@@ -764,6 +774,13 @@ def run_c3(eng, local, rank, world, sh, dev, ntx: int, steps: int, warmup: int):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     assert bool(ok.all()), "an honest transaction was rejected"
+    outputs = {"tx_ok": ok.cpu().numpy(), "tx_ids": ids.cpu().numpy()} if keep_outputs else None
+    if world > 1:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt[0])
+    if not phases:
+        return {"n": n, "ntx": ntx, "elapsed": elapsed, "leaves": nleaves, "outputs": outputs}
     # phases: the Merkle call (torch events on the same stream) and the verify kernels (HIP events)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     mk = []
@@ -776,13 +793,9 @@ def run_c3(eng, local, rank, world, sh, dev, ntx: int, steps: int, warmup: int):
     ph = np.mean(np.array([eng.verify_device_timed(local, n, *sig_args, sh) for _ in range(max(2, steps))]), axis=0)
     merkle_ms = float(np.mean(mk))
     comp = merkle_compressions(tb.leaf_len, tb.tx_begin)
-    if world > 1:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt[0])
     tb = None
     return {"n": n, "ntx": ntx, "elapsed": elapsed, "merkle_ms": merkle_ms, "phases": ph,
-            "leaves": nleaves, "compressions": comp}
+            "leaves": nleaves, "compressions": comp, "outputs": outputs}
 
 
 # SHA-256 instruction floor per compression on gfx950 (VALU lane-instructions, every one a VOP3 at the
@@ -906,6 +919,28 @@ def max_over_ranks(vals, device) -> list:
     tt = torch.tensor([float(v) for v in vals], dtype=torch.float64, device=device)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     return [float(x) for x in tt.cpu()]
+
+
+DUMP_BYTES = 48 << 20           # --dump-outputs: float32 payload of all the files together (the limit is 64 MB)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs DIR: each array of the last timed step's result as DIR/<name>.npy in float32 (verdict bits
+    and id bytes are exact in it).  The arrays share DUMP_BYTES equally; of one with more rows than its share
+    holds, a fixed seeded sample of rows (sorted, the same from run to run) is written."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20261019)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        rows = max(1, DUMP_BYTES // len(arrays) // (4 * max(1, a[0].size)))
+        if a.shape[0] > rows:
+            a = a[np.sort(rng.choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
+def verdict_bits(bitmap: torch.Tensor, n: int) -> np.ndarray:
+    """A device verdict bitmap (int64 words, bit i = signature i) as n host booleans."""
+    return native.bitmap_to_bools(bitmap.cpu().numpy().view(np.uint64), n)
 
 
 def c5_multi_line(eng, local, rank, world, sh, dev, n: int, steps: int) -> dict:
@@ -1047,6 +1082,14 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(MSG_BYTES))
     ap.add_argument("--n", type=int, default=0, help="signatures per GPU (default 1M for c2, 8M for c5)")
     ap.add_argument("--key-pool", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything else the line can carry: the other stream "
+                         "form, roofline, CPU baseline, C3 / C5 / keyed / host-buffer sub-lines, notary and resolve "
+                         "latency, the N > 1 sub-lines, and the detail file.  Off: set up, warm up, time the K steps, "
+                         "print the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32, at most "
+                         "64 MB in all: a fixed seeded sample of the rows of a larger array)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-notary", action="store_true")
@@ -1108,11 +1151,12 @@ def main():
     assert sh != 0
     if args.config == "c3":
         ntx = args.n or 1_000_000
-        r = run_c3(eng, local, rank, world, sh, dev, ntx, args.steps, args.warmup)
+        r = run_c3(eng, local, rank, world, sh, dev, ntx, args.steps, args.warmup, phases=args.full,
+                   keep_outputs=bool(args.dump_outputs))
         if rank == 0:
-            mad_rate, _ = eng.calibrate(local)
-            ph = r["phases"]
-            print(json.dumps({
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, r["outputs"])
+            line = {
                 "metric": "Ed25519 verifies/sec (node)", "value": world * r["n"] * args.steps / r["elapsed"],
                 "unit": "verifies/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": r["elapsed"] / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -1120,11 +1164,15 @@ def main():
                 "data": "synthetic (leaf blobs, keys, signatures generated on-GPU from seeded RNG)",
                 "config": {"workload": CONFIG_NAME["c3"], "txs_per_gpu": ntx, "signers_per_tx": 8,
                            "leaves_per_tx": 6, "sigs_per_gpu": r["n"], "parallelism": f"shard-by-transaction x{world}"},
-                "tx_ids_per_s": world * ntx * args.steps / r["elapsed"],
-                "phase_ms": {"merkle": r["merkle_ms"], "scalars": float(ph[0]), "points": float(ph[1]),
-                             "hs_straus": float(ph[2])},
-                "roofline": straus_roofline(eng, local, r["n"], float(ph[2]), float(ph.sum()), mad_rate),
-                "merkle_roofline": merkle_roofline(r["compressions"], ntx, r["merkle_ms"], mad_rate)}), flush=True)
+                "tx_ids_per_s": world * ntx * args.steps / r["elapsed"]}
+            if args.full:
+                mad_rate, _ = eng.calibrate(local)
+                ph = r["phases"]
+                line["phase_ms"] = {"merkle": r["merkle_ms"], "scalars": float(ph[0]), "points": float(ph[1]),
+                                    "hs_straus": float(ph[2])}
+                line["roofline"] = straus_roofline(eng, local, r["n"], float(ph[2]), float(ph.sum()), mad_rate)
+                line["merkle_roofline"] = merkle_roofline(r["compressions"], ntx, r["merkle_ms"], mad_rate)
+            print(json.dumps(line), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -1179,6 +1227,41 @@ def main():
     elapsed, gathered = timed(nstreams)
     assert written_all_ones(bitmaps[:min(nstreams, args.steps)], n), \
         "timed verify calls did not write an all-ones verdict bitmap (honest batch)"
+    if args.dump_outputs and rank == 0 and gathered is not None:
+        # what the last timed step handed back: its verdict bitmap (N > 1: the gathered one), one value per signature
+        dump_outputs(args.dump_outputs, {"verdicts": verdict_bits(gathered, world * n)})
+
+    def headline(value, elapsed):
+        return {
+            "metric": "Ed25519 verifies/sec (node)",
+            "value": value,
+            "unit": "verifies/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "uint32/uint64 (GF(2^255-19) radix 2^25.5 limbs, v_mad_u64_u32)",
+            "data": "synthetic (keys, messages, signatures generated on-GPU from seeded RNG, RFC 8032 signing)",
+            "config": {"workload": CONFIG_NAME[args.config], "sigs_per_gpu": n, "msg_bytes": msg_len,
+                       "key_pool": args.key_pool or "distinct", "parallelism": f"shard-by-signature x{world}",
+                       "device_streams": nstreams, "gpu_max_hw_queues": HW_QUEUES or "unset (HIP default 4)",
+                       "collective": "RCCL all_gather of verdict bitmaps" if world > 1 else "none"}}
+
+    if not args.full:
+        # the plain run ends here: the headline line of the timed steps above and nothing else
+        if world > 1:
+            (elapsed,) = max_over_ranks([elapsed], dev)
+            assert bool((gathered == -1).all()), "a rank rejected an honest signature"
+        if rank == 0:
+            print(json.dumps(headline(world * n * args.steps / elapsed, elapsed)), flush=True)
+        if world > 1:
+            dist.barrier(group=cpu_group)
+            dist.destroy_process_group()
+        eng.close()
+        return
     prod_bitmap = bitmap.clone()
     zero_bitmaps()
     other_streams = 2 if nstreams == 1 else 1
@@ -1293,23 +1376,8 @@ def main():
             D_["resolve_chain"] = resolve_chain_latency(eng, local, 30, cpu=(world == 1 and not args.no_cpu))
         r3 = lambda x: None if x is None else float(f"{x:.4g}")  # noqa: E731
         R = D_["roofline"]
-        result = {
-            "metric": "Ed25519 verifies/sec (node)",
-            "value": value,
-            "unit": "verifies/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "uint32/uint64 (GF(2^255-19) radix 2^25.5 limbs, v_mad_u64_u32)",
-            "data": "synthetic (keys, messages, signatures generated on-GPU from seeded RNG, RFC 8032 signing)",
-            "config": {"workload": CONFIG_NAME[args.config], "sigs_per_gpu": n, "msg_bytes": msg_len,
-                       "key_pool": args.key_pool or "distinct", "parallelism": f"shard-by-signature x{world}",
-                       "device_streams": nstreams, "gpu_max_hw_queues": HW_QUEUES or "unset (HIP default 4)",
-                       "collective": "RCCL all_gather of verdict bitmaps" if world > 1 else "none"},
+        result = headline(value, elapsed)
+        result.update({
             f"{other_key}_ms_per_step": r3(other_elapsed / args.steps * 1e3),
             f"{other_key}_value": r3(world * n * args.steps / other_elapsed),
             "roofline": {"bound": "valu", "achieved": r3(R["achieved"]), "peak": r3(R["peak"]), "unit": "Tmac/s",
@@ -1330,7 +1398,7 @@ def main():
                          # the 1M launch's partly filled last round is what separates frac from this
                          "frac_whole_rounds": r3(whole_rounds.get("frac")),
                          "whole_rounds_n": whole_rounds.get("n")},
-        }
+        })
         if "cpu_baseline" in D_:
             c = D_["cpu_baseline"]
             result["cpu_baseline"] = {"value": r3(c["value"]), "unit": c["unit"], "cores": c["cores"], "kind": c["kind"],

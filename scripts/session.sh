@@ -5,7 +5,7 @@
 #   tests            pytest -m gpu (one process)                      -> OUT/pytest.log
 #   smoke            __graft_entry__.smoke()                          -> OUT/smoke.log
 #   gpus2            bench.py --gpus 2 on a 1-GPU box (expects exit 2) -> OUT/gpus2.err
-#   bench[:ARGS]     bench.py ARGS (commas become spaces)             -> OUT/bench.json, OUT/bench_detail.json
+#   bench[:ARGS]     bench.py --full ARGS (commas become spaces)      -> OUT/bench.json, OUT/bench_detail.json
 #   prof[:ARGS]      the same bench command under rocprofv3 --kernel-trace --stats
 #                    -> OUT/kernel_stats.csv, OUT/trace_by_shape.txt
 #   pmc[:N]          PMC passes of the throughput kernels at N signatures (scripts/pmc.sh) -> OUT/pmc_N/, summary
@@ -38,11 +38,11 @@ for step in "$@"; do
       timeout -k 10 120 python -u bench.py --gpus 2 --steps 1 > "$OUT/gpus2.out" 2> "$OUT/gpus2.err"
       echo "exit $? (expect 2)"; tail -1 "$OUT/gpus2.err" ;;
     bench)
-      timeout -k 10 900 python -u bench.py --detail "$OUT/bench_detail.json" ${arg//,/ } > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 900 python -u bench.py --full --detail "$OUT/bench_detail.json" ${arg//,/ } > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     prof)
       timeout -k 10 1000 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o prof --output-format csv -- \
-          python3 -u bench.py --detail "$OUT/prof_bench_detail.json" ${arg//,/ } > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -30 "$OUT/prof_bench.err"; exit 1; }
+          python3 -u bench.py --full --detail "$OUT/prof_bench_detail.json" ${arg//,/ } > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -30 "$OUT/prof_bench.err"; exit 1; }
       find "$OUT/prof" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
       KT=$(find "$OUT/prof" -name "*kernel_trace.csv" | head -1)
       [ -n "$KT" ] && python3 tools/trace_by_shape.py "$KT" > "$OUT/trace_by_shape.txt" 2>&1

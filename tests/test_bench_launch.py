@@ -111,6 +111,50 @@ def test_visible_gpus_never_calls_hip(monkeypatch):
     assert launch.spawn(2, [sys.executable, "-c", "pass"], require_gpus=True) == 2
 
 
+def test_dump_outputs_float32_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: float32 files; an array past its share of the byte budget is cut to a sample of rows that is
+    the same in every run and keeps the rows' order; a small array is written whole."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+
+    rows = 3 * bench.DUMP_BYTES // (2 * 4 * 32)            # 3x its half of the budget at 32 values per row
+    big = np.zeros((rows, 32), np.uint8)
+    big[:, :4] = np.arange(rows, dtype="<u4").view(np.uint8).reshape(rows, 4)
+    big[:, 4:] = (np.arange(rows)[:, None] * 7 + np.arange(28)[None, :]) % 256
+    small = np.arange(1000) % 2 == 0
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert a.shape == (bench.DUMP_BYTES // 2 // (4 * 32), 32)
+    # every sampled row is a row of the input (its first three bytes spell its index), in the input's order
+    idx = (a[:, 0] + 256 * a[:, 1] + 65536 * a[:, 2]).astype(np.int64)
+    assert (np.diff(idx) > 0).all() and idx[-1] < rows and np.array_equal(a, big[idx].astype(np.float32))
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.astype(np.float32))
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64_000_000
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_its_verdicts(tmp_path):
+    """A plain run times its steps and prints the headline fields alone (the other legs belong to --full);
+    --dump-outputs writes one float32 verdict per signature of the last timed step, all 1 for the honest batch."""
+    import numpy as np
+    n = 6400 + 37
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--n", str(n), "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "verifies/s"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["higher_is_better"] is True and d["config"]["sigs_per_gpu"] == n
+    assert not {"roofline", "cpu_baseline", "host_api", "c3", "c5_shard", "keyed", "notary", "detail_file"} & set(d)
+    v = np.load(tmp_path / "out" / "verdicts.npy")
+    assert v.dtype == np.float32 and v.shape == (n,) and (v == 1).all()
+    assert os.listdir(tmp_path / "out") == ["verdicts.npy"]
+
+
 def _fake_node(root, idx, simd, minor):
     d = root / str(idx)
     d.mkdir(parents=True)
