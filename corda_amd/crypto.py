@@ -219,6 +219,53 @@ def verify_with_ecdsa(public_key: PublicKey, content: bytes, signature: OpaqueBy
         raise err
 
 
+# ---------------------------------------------------------------- key pairs and signing
+def _pack_messages(msgs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Messages back to back in one arena -> (arena, offsets, lengths)."""
+    m = len(msgs)
+    lens = np.fromiter((len(x) for x in msgs), np.uint32, count=m)
+    offs = np.zeros(m, np.uint64)
+    if m > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return np.frombuffer(b"".join(msgs) + b"\0" * 16, np.uint8), offs, lens
+
+
+class KeyPair:
+    """A java.security.KeyPair over Ed25519 as entropyToKeyPair / generateKeyPair build it
+    (CryptoUtilities.kt:117-130): `public` is the EdDSAPublicKey, the private half is a native.Signer
+    holding the expanded key on the GPU.  KeyPair.from_entropy(20) is DUMMY_NOTARY_KEY."""
+
+    def __init__(self, seed: bytes, engine: Optional[native.Engine] = None):
+        self._signer = native.Signer(engine or native.default_engine(), seed)
+        self.public = EdDSAPublicKey(self._signer.public_key)
+
+    @classmethod
+    def from_entropy(cls, entropy: int, engine: Optional[native.Engine] = None) -> "KeyPair":
+        """entropyToKeyPair(BigInteger): BigInteger.toByteArray().copyOf(32) is the seed."""
+        if entropy == 0:
+            raw = b"\x00"
+        else:
+            raw = entropy.to_bytes((entropy.bit_length() + 8) // 8, "big", signed=True)
+        return cls(raw[:32].ljust(32, b"\x00"), engine)
+
+    def close(self):
+        self._signer.close()
+
+    def sign_many(self, messages: Sequence[bytes]) -> List[DigitalSignature.WithKey]:
+        """One signWithECDSA per message, all in ONE GPU call."""
+        msgs = [bytes(x) for x in messages]
+        if not msgs:
+            return []
+        sigs = self._signer.sign(*_pack_messages(msgs))
+        return [DigitalSignature.WithKey(self.public, sigs[j].tobytes()) for j in range(len(msgs))]
+
+    def sign_with_ecdsa(self, bytes_to_sign) -> DigitalSignature.WithKey:
+        """KeyPair.signWithECDSA(bytesToSign: ByteArray | OpaqueBytes) (CryptoUtilities.kt:63-73, 80-81)."""
+        if isinstance(bytes_to_sign, OpaqueBytes):
+            bytes_to_sign = bytes_to_sign.bits
+        return self.sign_many([bytes_to_sign])[0]
+
+
 # ---------------------------------------------------------------- composite keys
 class CompositeKey:
     """CompositeKey.kt:22-148: weighted-threshold key tree; fulfilment is pure host logic."""

@@ -4,7 +4,8 @@
 //   cv_k_hs.hip    half-size throughput group: scalars, points (cv_k_hss.hip: hs_straus) — the C2/C3/C5 hot path
 //   cv_k_lat.hip   latency forms for notary-sized batches: fused prep, quad and tri-chain Straus
 //   cv_k_keyed.hip keyed per-key comb path (key tables, hash, comb, finish)
-//   cv_k_misc.hip  signing, Merkle ids, partial Merkle trees, calibration kernels
+//   cv_k_misc.hip  signing (synthetic inputs), Merkle ids, partial Merkle trees, calibration kernels
+//   cv_k_sign.hip  fixed-key signing (signer key expansion, one signature per lane)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -141,6 +142,14 @@ template <bool SEQ> __global__ void cv_hs_straus_quad_kernel(uint32_t n, uint32_
 __global__ void cv_gather16_kernel(const uint4 *src, uint4 *dst, size_t q);
 template <bool SEQ> __global__ void cv_hs_straus_tri_kernel(uint32_t n, uint32_t cap, const uint32_t *ws_dig, const uint32_t *ws_tab, const uint32_t *ws_tabR, const uint8_t *ws_ok, uint64_t *bitmap, uint8_t *nib);
 __global__ void cv_sign_kernel( uint32_t n, const uint8_t *seed, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint8_t *pk_out, uint8_t *sig_out);
+// fixed-key signing (cv_k_sign.hip): a signer's device record is a | prefix | abyte (24 words) + 8 words that
+// carry the seed into cv_key_expand_kernel, which clears them; waves per SIMD cv_sign_keyed_kernel is built for
+#define CV_SIGN_REC_WORDS 32
+#ifndef CV_SIGN_WAVES
+#define CV_SIGN_WAVES 2
+#endif
+__global__ void cv_key_expand_kernel(uint32_t *rec);
+__global__ void cv_sign_keyed_kernel(uint32_t n, const uint32_t *key_rec, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint8_t *sig_out, const uint32_t *bw16);
 // leaves per leaf-hash workgroup (each workgroup sorts 2 x CV_LEAF_BLOCK leaves by SHA-256 block count)
 #define CV_LEAF_BLOCK 256
 __global__ void cv_leaf_hash_pair_kernel(uint32_t nleaves, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint32_t *leaf_digest);

@@ -4,7 +4,7 @@
 //       PublicKey.verifyWithECDSA (reference core/src/main/kotlin/net/corda/core/crypto/CryptoUtilities.kt:90-96),
 //       in three forms by batch size (CvkPlan): throughput (scalars -> points -> hs_straus, one signature per
 //       lane), quad (4 lanes per signature) and tri-chain (16 lanes per signature) for notary-sized batches
-//   keyed comb, signing (synthetic inputs), Merkle tx ids
+//   keyed comb, signing (synthetic inputs; fixed-key for a notary's replies), Merkle tx ids
 //       (core/.../transactions/MerkleTransaction.kt:26-38,66-99), partial Merkle trees, calibration
 //
 // The kernels live in cv_k_*.hip (declarations: cv_kcommon.h).  No launcher state is global except the
@@ -287,6 +287,26 @@ hipError_t cvk_sign(uint32_t n, const uint8_t *seed, const uint8_t *arena, const
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (n + CV_BLOCK - 1) / CV_BLOCK;
     hipLaunchKernelGGL(cv_sign_kernel, dim3(blocks), dim3(CV_BLOCK), 0, stream, n, seed, arena, off, len, pk, sig);
+    return hipGetLastError();
+}
+
+// Fixed-key signing.  key_rec: CVK_SIGN_REC_BYTES of device memory (16-B aligned) with the seed in its last 32
+// bytes; the kernel leaves a | prefix | abyte in the first 96 and clears the seed.
+hipError_t cvk_key_expand(uint32_t *key_rec, hipStream_t stream) {
+    static_assert(CVK_SIGN_REC_BYTES == CV_SIGN_REC_WORDS * 4, "signer record size");
+    hipLaunchKernelGGL(cv_key_expand_kernel, dim3(1), dim3(CV_BLOCK), 0, stream, key_rec);
+    return hipGetLastError();
+}
+
+// n signatures with the expanded key in key_rec, [r]B from the device's CV_BW16 rows (shared with verify)
+hipError_t cvk_sign_keyed(uint32_t n, const uint32_t *key_rec, const uint8_t *arena, const uint64_t *off,
+                          const uint32_t *len, uint8_t *sig, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const uint32_t *bw16 = nullptr;
+    const hipError_t e = bw16_table(&bw16, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cv_sign_keyed_kernel, dim3((n + CV_BLOCK - 1) / CV_BLOCK), dim3(CV_BLOCK), 0, stream, n, key_rec,
+                       arena, off, len, sig, bw16);
     return hipGetLastError();
 }
 

@@ -42,6 +42,12 @@ hipError_t cvk_verify(const CvkPlan *plan, uint32_t n, const uint8_t *pk, const 
                       const CvkSplit *split, const CvkPrepOverlap *po);
 hipError_t cvk_sign(uint32_t n, const uint8_t *seed, const uint8_t *arena, const uint64_t *off, const uint32_t *len,
                     uint8_t *pk, uint8_t *sig, hipStream_t stream);
+// Fixed-key signing: a signer's device record (a | prefix | abyte, then 32 bytes that carry the seed into
+// cvk_key_expand and come back cleared), and n signatures with it.
+#define CVK_SIGN_REC_BYTES 128
+hipError_t cvk_key_expand(uint32_t *key_rec, hipStream_t stream);
+hipError_t cvk_sign_keyed(uint32_t n, const uint32_t *key_rec, const uint8_t *arena, const uint64_t *off,
+                          const uint32_t *len, uint8_t *sig, hipStream_t stream);
 hipError_t cvk_pmt_verify(uint32_t ntrees, const uint8_t *kind, const uint32_t *left, const uint32_t *right,
                           const uint8_t *leaf_hash, const uint32_t *tree_begin, const uint8_t *root, const uint8_t *check,
                           const uint32_t *check_begin, uint32_t *dig, uint8_t *flag, uint8_t *verdict, uint8_t *status,

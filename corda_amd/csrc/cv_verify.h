@@ -648,6 +648,98 @@ __host__ __device__ __forceinline__ void cv_sign_one(const uint32_t *btab, const
     for (int q = 0; q < 8; q++) { pk_out[q] = abyte[q]; sig_out[q] = rb[q]; sig_out[8 + q] = S[q]; }
 }
 
+// ---------------------------------------------------------------- fixed-key signing
+// A signer that holds ONE long-lived key (the notary's response signatures, NotaryFlow.kt:97-113; every
+// KeyPair.signWithECDSA call site, CryptoUtilities.kt:63-73): the key work of cv_sign_one — SHA-512 of the
+// seed, A = [a]B, A's encoding — is done once per signer (cv_key_expand), and the one scalar multiplication
+// a message needs reads the radix-2^16 basepoint rows the verify kernels already keep on the device:
+// 48 doublings and 16 mixed additions instead of 2 x (248 + 32).  Signatures are RFC 8032's, bit for bit
+// cv_sign_one's.
+
+// EdDSAPrivateKeySpec(seed): a = clamp(SHA-512(seed)[0:32]), prefix = SHA-512(seed)[32:64], abyte = enc([a]B).
+// Once per signer: not a hot path.
+__host__ __device__ __forceinline__ void cv_key_expand(const uint32_t seed[8], uint32_t a[8], uint32_t prefix[8],
+                                                       uint32_t abyte[8], const uint32_t *btab) {
+    uint32_t sd[16], hd[16];
+#pragma unroll
+    for (int q = 0; q < 8; q++) { sd[q] = seed[q]; sd[8 + q] = 0; }
+    sha512_pre_msg(hd, sd, 32, nullptr, 0);            // h = SHA-512(seed)
+#pragma unroll
+    for (int q = 0; q < 8; q++) { a[q] = hd[q]; prefix[q] = hd[8 + q]; }
+    a[0] &= 0xfffffff8u;                               // clamp: h[0] &= 248
+    a[7] &= 0x3fffffffu;                               //        h[31] &= 63
+    a[7] |= 0x40000000u;                               //        h[31] |= 64
+    ge_p3 A;
+    ge_scalarmult_base(A, a, btab);
+    ge_p3_encode(abyte, A);
+}
+
+// [k]B for a scalar k < 2^253 from the CV_BW16 rows (row j, entry m = m * 2^(64 j) * B): k's 16 signed
+// radix-2^16 digits d_(4j + c) (digits65536_pairs: |d| <= 2^15, the rows' last entry; for k < 2^253 the top
+// digit is at most 2^13 + 1, so no carry leaves it) are added column by column,
+//     [k]B = sum_c 2^(16 c) sum_j d_(4j + c) * 2^(64 j) * B,
+// c = 3 .. 0 with 16 doublings between columns: 48 doublings and 16 mixed additions.
+__host__ __device__ __forceinline__ void ge_scalarmult_base_w16(ge_p3 &R, const uint32_t k[8], const uint32_t *bw16) {
+    uint32_t kd[8];
+    digits65536_pairs(kd, k);                          // kd[i] = d_i | d_(i + 8) << 16
+    ge_p3_identity(R);
+    ge_p1p1 t;
+#pragma unroll 1
+    for (int c = 3; c >= 0; c--) {
+        if (c != 3) {
+            ge_p2 q;
+            ge_p3_to_p2(q, R);
+#pragma unroll 1
+            for (int d = 0; d < 15; d++) {
+                ge_p2_dbl(t, q);
+                ge_p1p1_to_p2(q, t);
+            }
+            ge_p2_dbl(t, q);
+            ge_p1p1_to_p3(R, t);
+        }
+#pragma unroll
+        for (int j = 0; j < CV_BW16_ROWS; j++) {
+            // digit 4j + c: the low half of pair word 4j + c (j < 2) or the high half of word 4j + c - 8
+            const uint32_t word = sel8(kd, 4 * (j & 1) + c);
+            const int d = j < 2 ? (int)(int16_t)(word & 0xffffu) : (int)word >> 16;
+            ge_precomp e;
+            btab_select(e, bw16 + (size_t)j * CV_BW16_ROW, d);
+            ge_madd(t, R, e);
+            ge_p1p1_to_p3(R, t);
+        }
+    }
+}
+
+// EdDSAEngine.sign with an expanded key (RFC 8032 5.1.6): r = SHA-512(prefix || M) mod L, R = [r]B,
+// k = SHA-512(R || Abyte || M) mod L, S = (r + k a) mod L.  sig_out = R || S.
+__host__ __device__ __forceinline__ void cv_sign_keyed_one(const uint32_t *bw16, const uint32_t a[8],
+                                                           const uint32_t prefix[8], const uint32_t abyte[8],
+                                                           const uint8_t *msg, uint32_t mlen, uint32_t sig_out[16]) {
+    uint32_t r[8], rb[8], k[8], S[8];
+    {
+        uint32_t pre[16], rd[16];
+#pragma unroll
+        for (int q = 0; q < 8; q++) { pre[q] = prefix[q]; pre[8 + q] = 0; }
+        sha512_pre_msg(rd, pre, 32, msg, mlen);
+        sc_reduce512(r, rd);
+    }
+    {
+        ge_p3 Rp;
+        ge_scalarmult_base_w16(Rp, r, bw16);
+        ge_p3_encode(rb, Rp);
+    }
+    {
+        uint32_t pre[16], kd[16];
+#pragma unroll
+        for (int q = 0; q < 8; q++) { pre[q] = rb[q]; pre[8 + q] = abyte[q]; }
+        sha512_pre_msg(kd, pre, 64, msg, mlen);
+        sc_reduce512(k, kd);
+    }
+    sc_muladd(S, k, a, r);
+#pragma unroll
+    for (int q = 0; q < 8; q++) { sig_out[q] = rb[q]; sig_out[8 + q] = S[q]; }
+}
+
 // ---------------------------------------------------------------- Merkle root of one transaction
 // MerkleTree.buildMerkleTree over cnt leaf digests (8 big-endian words each), in place.
 // Returns false for an empty leaf list (MerkleTreeException).  root = 8 big-endian words.

@@ -34,6 +34,8 @@ EXPORTED = (
     "cv_merkle_tx_ids_async", "cv_set_option", "cv_get_option", "cv_diag_stats",
     "cv_verify_transactions", "cv_verify_transactions_async", "cv_open_ex", "cv_msg_extent",
     "cv_ed25519_verify_batch_ex", "cv_merkle_tx_ids_bounded", "cv_verify_transactions_ex",
+    "cv_signer_open", "cv_signer_public_key", "cv_signer_close", "cv_ed25519_sign_keyed",
+    "cv_ed25519_sign_keyed_device",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -141,6 +143,16 @@ def load():
         lib.cv_ed25519_verify_device_timed.restype = ctypes.c_int
         lib.cv_ed25519_sign_device.argtypes = [_vp, ctypes.c_int, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.cv_ed25519_sign_device.restype = ctypes.c_int
+        lib.cv_signer_open.argtypes = [_vp, _vp, ctypes.POINTER(_vp)]
+        lib.cv_signer_open.restype = ctypes.c_int
+        lib.cv_signer_public_key.argtypes = [_vp, _vp]
+        lib.cv_signer_public_key.restype = ctypes.c_int
+        lib.cv_signer_close.argtypes = [_vp]
+        lib.cv_signer_close.restype = None
+        lib.cv_ed25519_sign_keyed.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp]
+        lib.cv_ed25519_sign_keyed.restype = ctypes.c_int
+        lib.cv_ed25519_sign_keyed_device.argtypes = [_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
+        lib.cv_ed25519_sign_keyed_device.restype = ctypes.c_int
         lib.cv_merkle_tx_ids_device.argtypes = [_vp, ctypes.c_int, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.cv_merkle_tx_ids_device.restype = ctypes.c_int
         lib.cv_synchronize.argtypes = [_vp, ctypes.c_int]
@@ -231,9 +243,12 @@ class Engine:
         self._h = h
         self.mu = threading.Lock()
         self._inflight = {}
+        self._signers = weakref.WeakSet()   # open Signer objects: a signer is closed before its context
 
     def close(self):
         if self._h:
+            for s in list(self._signers):
+                s.close()
             self._lib.cv_close(self._h)
             self._h = None
 
@@ -562,6 +577,71 @@ class Engine:
 
     def synchronize(self, device: int):
         _check(self._lib.cv_synchronize(self._h, device), "cv_synchronize")
+
+
+class Signer:
+    """One Ed25519 key bound to an engine (cv_signer): the key is expanded once on every device, then
+    sign() / sign_device() sign batches with it — KeyPair.signWithECDSA (CryptoUtilities.kt:63-73) for a
+    holder of one long-lived key, such as a notary.  Immutable after construction: several threads may sign
+    with it at once.  close() (or the with-statement) wipes the device records; the engine closes the
+    signers still open when it is closed itself."""
+
+    def __init__(self, engine: Engine, seed):
+        seed = np.frombuffer(bytes(seed), np.uint8)
+        if seed.size != 32:
+            raise ValueError("seed must be 32 bytes")
+        self._engine = engine
+        self._lib = engine._lib
+        h = _vp()
+        _check(self._lib.cv_signer_open(engine._h, _p(seed), ctypes.byref(h)), "cv_signer_open")
+        self._h = h
+        pk = np.zeros(32, np.uint8)
+        _check(self._lib.cv_signer_public_key(h, _p(pk)), "cv_signer_public_key")
+        self.public_key = pk.tobytes()
+        engine._signers.add(self)
+
+    def close(self):
+        if self._h:
+            self._lib.cv_signer_close(self._h)
+            self._h = None
+            self._engine._signers.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sign(self, arena, off, ln) -> np.ndarray:
+        """arena u8, off u64[n], ln u32[n] -> sig (n,64) u8, one signature per message, in one call."""
+        if not self._h:
+            raise ValueError("the signer is closed")
+        arena = _u8(arena) if arena is not None and np.asarray(arena).size else np.zeros(16, np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        ln = np.ascontiguousarray(ln, dtype=np.uint32)
+        n = off.shape[0]
+        if ln.shape[0] != n:
+            raise ValueError("off/len must have n entries")
+        sig = np.zeros((n, 64), np.uint8)
+        rc = self._lib.cv_ed25519_sign_keyed(self._engine._h, self._h, n, _p(arena), arena.size, _p(off), _p(ln),
+                                             _p(sig))
+        if rc == -3 and n and _msg_end(self._lib, off, ln) > arena.size:
+            raise ValueError("message range exceeds the arena")
+        _check(rc, "cv_ed25519_sign_keyed")
+        return sig
+
+    def sign_device(self, device: int, n: int, d_arena: int, d_off: int, d_len: int, d_sig: int, stream: int = 0):
+        """Device pointers in, d_sig[n][64] out; enqueued on stream (0: the device's own), not synchronised."""
+        if not self._h:
+            raise ValueError("the signer is closed")
+        _check(self._lib.cv_ed25519_sign_keyed_device(self._engine._h, device, self._h, n, d_arena, d_off, d_len,
+                                                      d_sig, stream or None), "cv_ed25519_sign_keyed_device")
 
 
 def dedupe_keys(pk: np.ndarray):

@@ -37,7 +37,8 @@ import numpy as np
 
 from . import native
 from .crypto import (CompositeKey, DigitalSignature, EdDSAPublicKey, IllegalArgumentException, IllegalStateException,
-                     InvalidKeyException, SignatureException, VerifyItem, _prefilter, verify_many, verify_with_ecdsa)
+                     InvalidKeyException, KeyPair, SignatureException, VerifyItem, _prefilter, verify_many,
+                     verify_with_ecdsa)
 from .transactions import (MerkleTreeException, SecureHash, SignaturesMissingException, SignedTransaction,
                            WireTransaction, compute_ids)
 
@@ -197,10 +198,9 @@ class BatchingNotary:
                  uniqueness=None,
                  timestamp_checker: Optional[TimestampChecker] = None, group=None):
         self.engine = engine or native.default_engine()
-        self.seed = np.frombuffer(bytes(notary_seed), np.uint8).reshape(1, 32)
-        pk, _ = self.engine.sign_batch(self.seed, np.zeros(16, np.uint8), np.zeros(1, np.uint64),
-                                       np.zeros(1, np.uint32))
-        self.public_key = EdDSAPublicKey(pk[0].tobytes())
+        # the notary's one long-lived key, expanded once on the engine's devices (cv_signer)
+        self.key_pair = KeyPair(bytes(notary_seed), self.engine)
+        self.public_key: EdDSAPublicKey = self.key_pair.public
         self.owning_key: CompositeKey = self.public_key.composite
         self.validating = validating
         self.uniqueness = uniqueness if uniqueness is not None else InMemoryUniquenessProvider()
@@ -213,15 +213,8 @@ class BatchingNotary:
         return verify_many(items, self.engine)
 
     def _sign(self, msgs: List[bytes]) -> List[DigitalSignature.WithKey]:
-        """The notary key over every message, in one GPU signing call."""
-        m = len(msgs)
-        lens = np.fromiter((len(x) for x in msgs), np.uint32, count=m)
-        offs = np.zeros(m, np.uint64)
-        if m > 1:
-            offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-        arena = np.frombuffer(b"".join(msgs) + b"\0" * 16, np.uint8)
-        _, sigs = self.engine.sign_batch(np.repeat(self.seed, m, axis=0), arena, offs, lens)
-        return [DigitalSignature.WithKey(self.public_key, sigs[j].tobytes()) for j in range(m)]
+        """The notary key over every message, in one GPU signing call (the fixed-key signer)."""
+        return self.key_pair.sign_many(msgs)
 
     def notarise(self, requests: Sequence[SignRequest]) -> List[Result]:
         n = len(requests)

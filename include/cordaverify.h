@@ -21,6 +21,11 @@
  *   cv_ed25519_sign_batch     N x  PrivateKey.signWithECDSA(bytes) after entropyToKeyPair/seed
  *                                 CryptoUtilities.kt:63-73,123-130 (deterministic RFC 8032; used to
  *                                 generate synthetic workloads, not on the validation path)
+ *   cv_signer_open +          N x  KeyPair.signWithECDSA(bytes) with ONE long-lived key
+ *   cv_ed25519_sign_keyed         CryptoUtilities.kt:63-73,80-87: the notary's reply signatures, sign(stx.id) and
+ *                                 the signed conflict report (NotaryFlow.kt:97-113,133-141; SignedData.kt),
+ *                                 and every node's own-key signing.  The same RFC 8032 signatures as
+ *                                 cv_ed25519_sign_batch, with the key expanded once.
  *   cv_tx_verdicts            per-transaction AND of signature verdicts (the "all sigs valid" half of
  *                                 SignedTransaction.verifySignatures, SignedTransaction.kt:58-72)
  *   cv_verify_transactions    N x  SignedTransaction.verifySignatures' id + signature checks in one call
@@ -203,6 +208,36 @@ int cv_ed25519_sign_batch(cv_ctx *ctx, size_t n, const uint8_t *seed /* n*32 */,
                           const uint64_t *msg_off, const uint32_t *msg_len, uint8_t *pk_out /* n*32 */,
                           uint8_t *sig_out /* n*64 */);
 
+/* A signer: one Ed25519 private key (EdDSAPrivateKeySpec(seed), the KeyPair of entropyToKeyPair / generateKeyPair,
+ * CryptoUtilities.kt:117-130) expanded once on every device of the context — the clamped scalar a, the hash prefix
+ * and the encoded public key A = [a]B: a 128-byte device record per device (96 bytes of key record, and 32 bytes
+ * that carry the seed to the expansion kernel, which clears them).  It is what a notary holds for its
+ * replies (NotaryFlow.kt:97-113: sign(stx.id); :133-141: the SignedData conflict report, SignedData.kt) and a node
+ * for its own signatures (PrivateKey.signWithECDSA, CryptoUtilities.kt:63-73).
+ * cv_signer_open returns the usual codes; the seed is copied to the devices through pinned memory that is wiped
+ * before the call returns, and the library keeps no host copy of the seed, a or the prefix.  The wiping covers
+ * what the library allocates: the expansion kernel also uses 48 bytes per lane of the device's scratch memory
+ * (as cv_ed25519_sign_batch's kernel uses 112), where words derived from the seed may remain until the device
+ * reuses it; the signing kernel itself uses no scratch.  A signer is immutable
+ * after open: any number of threads may sign with it at once, under the context's rules above.  cv_signer_close
+ * waits for the devices, overwrites the device records and frees them (NULL: no-op); a signer is closed before
+ * its context. */
+typedef struct cv_signer cv_signer;
+int cv_signer_open(cv_ctx *ctx, const uint8_t seed[32], cv_signer **out);
+/* The signer's public key, KeyPair.public's 32 encoded bytes (EdDSAPublicKey.abyte; CryptoUtilities.kt:71-73, 80). */
+int cv_signer_public_key(const cv_signer *s, uint8_t pk[32]);
+void cv_signer_close(cv_signer *s);
+
+/* N x KeyPair.signWithECDSA(bytesToSign) with the signer's key (CryptoUtilities.kt:63-73, 80; the notary's
+ * NotaryFlow.kt:97-113 replies in one call): RFC 8032 deterministic signatures, bit for bit those of
+ * cv_ed25519_sign_batch with the seed repeated n times, sig_out[i] = R || S over message i.  The batch is routed
+ * over the context's devices like cv_ed25519_sign_batch (shards in multiples of 64).  n == 0 returns CV_OK and
+ * touches nothing; a record whose msg_off + msg_len exceeds msg_arena_bytes, or wraps, returns CV_E_ARGS before
+ * any copy or launch (msg_arena_bytes = UINT64_MAX: unchecked). */
+int cv_ed25519_sign_keyed(cv_ctx *ctx, const cv_signer *s, size_t n, const uint8_t *msg_arena,
+                          uint64_t msg_arena_bytes, const uint64_t *msg_off, const uint32_t *msg_len,
+                          uint8_t *sig_out /* n*64 */);
+
 /* tx_ok[t] = AND of verdict bits [tx_sig_begin[t], tx_sig_begin[t+1]); a transaction with no
  * signatures is not ok (SignedTransaction requires sigs.isNotEmpty(), SignedTransaction.kt:27-29). */
 int cv_tx_verdicts(size_t ntx, const uint64_t *verdict_bitmap, const uint32_t *tx_sig_begin, uint8_t *tx_ok);
@@ -275,6 +310,13 @@ int cv_ed25519_verify_device_keyed(cv_ctx *ctx, int device, size_t n, size_t nke
 
 int cv_ed25519_sign_device(cv_ctx *ctx, int device, size_t n, const void *d_seed, const void *d_arena,
                            const void *d_off, const void *d_len, void *d_pk, void *d_sig, void *stream);
+
+/* Device-resident form of cv_ed25519_sign_keyed (KeyPair.signWithECDSA, CryptoUtilities.kt:63-73; NotaryFlow.kt:97-113):
+ * d_sig[n][64] from the signer's record on `device`; enqueued on `stream` (NULL: the device's own) without
+ * synchronising, like cv_ed25519_verify_device, so a verify of the signatures queued behind it on the same stream
+ * reads them complete.  The signer stays open until that work has finished. */
+int cv_ed25519_sign_keyed_device(cv_ctx *ctx, int device, const cv_signer *s, size_t n, const void *d_arena,
+                                 const void *d_off, const void *d_len, void *d_sig, void *stream);
 
 /* d_workspace: nleaves * 32 bytes (leaf digests, overwritten) */
 int cv_merkle_tx_ids_device(cv_ctx *ctx, int device, size_t ntx, size_t nleaves, const void *d_arena,
