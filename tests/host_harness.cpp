@@ -311,6 +311,13 @@ int cvh_halfsize(const uint8_t *h, const uint8_t *s, uint8_t *out, int *v_neg, i
     return ok ? 1 : 0;
 }
 
+// cv_r_canonical on a 32-byte encoding: 1 iff the bytes re-encode to themselves (y < p; x = 0 only with sign 0).
+int cvh_r_canonical(const uint8_t *enc32) {
+    uint32_t w[8];
+    words_from_bytes(w, enc32, 8);
+    return cv_r_canonical(w) ? 1 : 0;
+}
+
 // The device's reciprocal sequence in cv_qdiv on the host (0 = exact division), for the lattice tests.
 void cvh_set_rcp_emulation(double rel_err) { cv_rcp_emulation = rel_err; }
 

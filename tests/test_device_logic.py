@@ -8,6 +8,7 @@ import random
 import numpy as np
 import pytest
 
+import device_vectors as V
 import ed25519_ref as E
 
 P, L = E.P, E.L
@@ -28,8 +29,7 @@ def _int(o):
 def test_field_ops_random_and_extreme(host_harness):
     H = host_harness
     rng = random.Random(1)
-    vals = [0, 1, 2, 19, P - 1, P, P + 1, P + 18, 2**255 - 1, 2**254, 2**128 + 7] + \
-           [rng.randrange(2**255) for _ in range(300)]
+    vals = V.field_values(rng)
     for a in vals:
         c = rng.choice(vals)
         o = _out(32)
@@ -43,11 +43,7 @@ def test_field_ops_random_and_extreme(host_harness):
         assert _int(o) == pow(a, P - 2, P)
 
 
-OFF = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
-
-
-def _limb_val(v):
-    return sum(x * (1 << o) for x, o in zip(v, OFF))
+_limb_val = V.limb_val
 
 
 def test_field_mul_at_limb_bounds(host_harness):
@@ -55,11 +51,9 @@ def test_field_mul_at_limb_bounds(host_harness):
     sq f <= 3.3M.  The harness is built with CV_BOUNDS_CHECK, so it also asserts the preconditions."""
     H = host_harness
     rng = random.Random(2)
-    W = [26, 25] * 5
 
     def limbs(mult):
-        return [min(int(rng.choice([mult, mult * 0.999, rng.random() * mult, 0.0]) * (1 << W[i])),
-                    int(mult * (1 << W[i])) - 1) for i in range(10)]
+        return V.limbs(rng, mult)
 
     for trial in range(400):
         a = limbs(8.0)
@@ -82,11 +76,9 @@ def test_interleaved_mul_sq_at_limb_bounds(host_harness):
     the precondition edges: mul f <= 8M, g <= 3.3M; sq f <= 3.3M, chain 2 doubled."""
     H = host_harness
     rng = random.Random(12)
-    W = [26, 25] * 5
 
     def limbs(mult):
-        return [min(int(rng.choice([mult, mult * 0.999, rng.random() * mult, 0.0]) * (1 << W[i])),
-                    int(mult * (1 << W[i])) - 1) for i in range(10)]
+        return V.limbs(rng, mult)
 
     for trial in range(150):
         a = [limbs(8.0) for _ in range(4)]
@@ -106,10 +98,7 @@ def test_interleaved_mul_sq_at_limb_bounds(host_harness):
 def test_sc_reduce(host_harness):
     H = host_harness
     rng = random.Random(3)
-    cases = [bytes(64), b"\xff" * 64, L.to_bytes(64, "little"), (L - 1).to_bytes(64, "little"),
-             (2 * L).to_bytes(64, "little"), (2**512 - L).to_bytes(64, "little")]
-    cases += [rng.getrandbits(512).to_bytes(64, "little") for _ in range(3000)]
-    for x in cases:
+    for x in V.sc_reduce_cases(rng):
         o = _out(32)
         H.cvh_sc_reduce(_b(x), o)
         assert _int(o) == int.from_bytes(x, "little") % L
@@ -195,7 +184,7 @@ def test_sha512_and_sha256(host_harness):
     import hashlib
     H = host_harness
     rng = random.Random(7)
-    for ln in [0, 1, 31, 47, 48, 49, 55, 56, 57, 63, 64, 111, 112, 113, 119, 120, 121, 127, 128, 200, 300, 1000]:
+    for ln in V.SHA_LENGTHS:
         pre = bytes(rng.randrange(256) for _ in range(64))
         m = bytes(rng.randrange(256) for _ in range(ln))
         o = _out(64)
@@ -206,7 +195,7 @@ def test_sha512_and_sha256(host_harness):
         o2 = _out(32)
         H.cvh_sha256(_b(m), ln, o2)
         assert bytes(o2) == hashlib.sha256(m).digest()
-        for shift in (1, 2, 3, 5):                       # unaligned message starts
+        for shift in V.SHA_SHIFTS:                       # unaligned message starts
             buf = (ctypes.c_uint8 * (ln + 16)).from_buffer_copy(bytes(shift) + m + bytes(16 - shift))
             H.cvh_sha512(_b(pre), 64, ctypes.byref(buf, shift), ln, o)
             assert bytes(o) == hashlib.sha512(pre + m).digest()
@@ -311,15 +300,7 @@ def test_exact_loop_quotients_just_below_integers(host_harness, rcp):
     H = host_harness
     H.cvh_exact_step.restype = ctypes.c_uint32
     rng = random.Random(99 + int(rcp * 2 ** 30))
-    cases = []
-    for _ in range(4000):
-        r1 = rng.randrange(2 ** 128, 2 ** rng.randrange(129, 225))
-        k = rng.choice([1, 2, 3, rng.randrange(2, 2 ** 32), 2 ** 32 - 1, 2 ** rng.randrange(1, 32)])
-        for d in (0, 1, 2, rng.randrange(1, 2 ** 20), -1, -rng.randrange(1, 2 ** 20)):
-            r0 = k * r1 - d
-            if r1 <= r0 < 2 ** 256:
-                cases.append((r0, r1))
-    for r0, r1 in cases:
+    for r0, r1 in V.exact_step_cases(rng):
         out = _out(32)
         q = H.cvh_exact_step(_b(r0.to_bytes(32, "little")), _b(r1.to_bytes(32, "little")), out)
         rem = int.from_bytes(bytes(out), "little")
@@ -336,8 +317,7 @@ def test_halfsize_lattice_properties(host_harness, rcp):
     and with the device's reciprocal sequence emulated (rcp)."""
     H = host_harness
     rng = random.Random(7)
-    cases = [(0, 0), (1, 5), (L - 1, L - 1), (2**128 - 1, 3), (2**128, 1), (2**252, 7), (8, 9)]
-    cases += [(rng.randrange(L), rng.randrange(L)) for _ in range(3000)]
+    cases = V.halfsize_cases(rng)
     wins = []
     fallbacks = 0
     for ci, (h, s) in enumerate(cases):
@@ -357,7 +337,7 @@ def test_halfsize_lattice_properties(host_harness, rcp):
             wins.append(nw.value)
         else:
             fallbacks += 1
-            assert ci < 7, "fallback on a random scalar"    # only degenerate edge lattices fall back
+            assert ci < V.HALFSIZE_EDGES, "fallback on a random scalar"    # only degenerate edge lattices fall back
             assert (u, v, nw.value) == (h, 1, 64)
     assert fallbacks <= 3
     assert sum(wins) / len(wins) < 34.0
@@ -424,11 +404,7 @@ def test_tri_digit_words(host_harness, rcp):
     H = host_harness
     H.cvh_tri_digit_words_mismatch.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     rng = random.Random(2024)
-    L = 2**252 + 27742317777372353535851937790883648493
-    hs = [0, 1, 2**128, 2**252, L - 1, 2**253 - 1, int("8" * 63, 16) % L, int("7" * 63, 16) % L]
-    hs += [rng.randrange(L) for _ in range(2000)]
-    for i, h in enumerate(hs):
-        s = rng.randrange(L) if i % 3 else (L - 1 - i)
+    for h, s in V.tri_digit_scalars(rng):
         assert H.cvh_tri_digit_words_mismatch(h.to_bytes(32, "little"), s.to_bytes(32, "little")) == 0, (hex(h), hex(s))
 
 
@@ -490,29 +466,8 @@ def test_limb_bounds_on_max_limb_encodings(host_harness):
     y = 2^255 - 2^j, both sign bits; S at 2^256 - 1, 2^255 and around L; verdicts and key status equal the
     oracle's."""
     H = host_harness
-    rng = random.Random(20261018)
-    ys = [(1 << 255) - 1 - k for k in range(64)] + [(1 << 255) - (1 << j) for j in range(1, 255, 7)]
-    encs = []
-    for y in ys:
-        for sign in (0, 1):
-            e = (y | (sign << 255)).to_bytes(32, "little")
-            try:
-                E.decode_point_0_1_0(e)
-                encs.append(e)
-            except Exception:
-                pass
-    assert len(encs) >= 40
-    svals = [(1 << 256) - 1, 1 << 255, (1 << 255) + 12345, L, L - 1, L + 1, (1 << 253) + rng.getrandbits(200)]
-    cases = []
-    for _ in range(160):
-        pk, r = rng.choice(encs), rng.choice(encs)
-        s = rng.choice(svals)
-        cases.append((pk, r + s.to_bytes(32, "little"), rng.randbytes(rng.choice([0, 32, 300]))))
-    # the same max-limb R over a real key, and honest signatures rewritten to the non-canonical key encoding
-    seed = bytes(range(32))
-    pk_h = E.public_key_of(seed)
-    for r in encs[:24]:
-        cases.append((pk_h, r + ((1 << 256) - 1).to_bytes(32, "little"), b"corda"))
+    encs, cases = V.max_limb_cases()
+    assert len(cases) == 184
     bad = []
     sc = (ctypes.c_uint32 * 73)()
     for pk, sig, m in cases:
