@@ -6,6 +6,7 @@
 //   cv_k_keyed.hip keyed per-key comb path (key tables, hash, comb, finish)
 //   cv_k_misc.hip  signing (synthetic inputs), Merkle ids, partial Merkle trees, calibration kernels
 //   cv_k_sign.hip  fixed-key signing (signer key expansion, one signature per lane)
+//   cv_k_pmt.hip   partial Merkle tree build (tear-offs): count, scan, emit
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -157,6 +158,10 @@ __global__ void cv_merkle_tree_kernel(uint32_t ntx, uint32_t leaf_base, const ui
 __global__ void cv_tx_sig_refs_kernel(uint32_t m, uint32_t c0, uint32_t nt, uint32_t s0, const uint32_t *tsb, uint64_t *off, uint32_t *len);
 __global__ void cv_tx_verdict_kernel(uint32_t nt, uint32_t s0, const uint32_t *tsb, const uint8_t *mstatus, const uint64_t *bitmap, uint8_t *tx_ok);
 __global__ void cv_pmt_verify_kernel(uint32_t ntrees, const uint8_t *kind, const uint32_t *left, const uint32_t *right, const uint8_t *leaf_hash, const uint32_t *tree_begin, const uint8_t *root, const uint8_t *check, const uint32_t *check_begin, uint32_t *dig, uint8_t *flag, uint8_t *verdict, uint8_t *status);
+// partial Merkle tree build (cv_k_pmt.hip, cv_pmt_build.h): one lane per transaction, a one-workgroup scan between
+__global__ void cv_pmt_count_kernel(uint32_t ntx, const uint8_t *leaf_hash, const uint32_t *leaf_dig, const uint32_t *tx_leaf_begin, const uint8_t *include, const uint32_t *include_begin, const uint8_t *keep, const uint32_t *ws_off, uint32_t *dig, uint8_t *flag, uint32_t *size, uint32_t *pos, uint8_t *ids, uint8_t *status, uint32_t *count);
+__global__ void cv_pmt_scan_kernel(uint32_t n, const uint32_t *count, uint32_t *tree_begin);
+__global__ void cv_pmt_emit_kernel(uint32_t ntx, const uint32_t *tx_leaf_begin, const uint32_t *ws_off, const uint32_t *dig, const uint8_t *flag, const uint32_t *size, uint32_t *pos, const uint8_t *status, const uint32_t *tree_begin, uint8_t *kind, uint32_t *left, uint32_t *right, uint8_t *node_hash);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

@@ -320,6 +320,21 @@ hipError_t cvk_pmt_verify(uint32_t ntrees, const uint8_t *kind, const uint32_t *
     return hipGetLastError();
 }
 
+// PartialMerkleTree.build for ntx transactions: the count sweep, the one-workgroup scan of the node counts and the
+// emit sweep, in order on the stream (a transaction's emit reads only its own pyramid and its tree_begin entry)
+hipError_t cvk_pmt_build(uint32_t ntx, const CvkPmtBuild *a, hipStream_t stream) {
+    if (ntx == 0) return hipSuccess;
+    if (!a || (a->leaf_hash != nullptr) == (a->leaf_dig != nullptr)) return hipErrorInvalidValue;
+    const dim3 grid((ntx + CV_BLOCK - 1) / CV_BLOCK), block(CV_BLOCK);
+    hipLaunchKernelGGL(cv_pmt_count_kernel, grid, block, 0, stream, ntx, a->leaf_hash, a->leaf_dig, a->tx_leaf_begin,
+                       a->include, a->include_begin, a->keep, a->ws_off, a->dig, a->flag, a->size, a->pos, a->ids,
+                       a->status, a->count);
+    hipLaunchKernelGGL(cv_pmt_scan_kernel, dim3(1), block, 0, stream, ntx, a->count, a->tree_begin);
+    hipLaunchKernelGGL(cv_pmt_emit_kernel, grid, block, 0, stream, ntx, a->tx_leaf_begin, a->ws_off, a->dig, a->flag,
+                       a->size, a->pos, a->status, a->tree_begin, a->kind, a->left, a->right, a->node_hash);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

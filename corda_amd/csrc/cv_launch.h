@@ -52,6 +52,29 @@ hipError_t cvk_pmt_verify(uint32_t ntrees, const uint8_t *kind, const uint32_t *
                           const uint8_t *leaf_hash, const uint32_t *tree_begin, const uint8_t *root, const uint8_t *check,
                           const uint32_t *check_begin, uint32_t *dig, uint8_t *flag, uint8_t *verdict, uint8_t *status,
                           hipStream_t stream);
+// Partial Merkle tree build of ntx transactions (cv_pmt_build.h): count -> scan -> emit on one stream.  The leaves are
+// leaf_hash (bytes) or leaf_dig (the leaf kernel's digest words), exactly one non-null; the include lists are
+// include / include_begin, or keep (one byte per leaf) when keep is non-null.  ws_off[ntx + 1]: each transaction's
+// first entry of the level pyramid (dig 8 words, flag, size, pos per entry).  The node arrays must hold the
+// batch's bound (cv_partial_merkle_build_bound): the kernels write tree_begin[ntx] records at the most that many.
+struct CvkPmtBuild {
+    const uint8_t *leaf_hash;
+    const uint32_t *leaf_dig;
+    const uint32_t *tx_leaf_begin;
+    const uint8_t *include;
+    const uint32_t *include_begin;
+    const uint8_t *keep;
+    const uint32_t *ws_off;
+    uint32_t *dig;
+    uint8_t *flag;
+    uint32_t *size, *pos, *count;
+    uint8_t *ids, *status;
+    uint32_t *tree_begin;
+    uint8_t *kind;
+    uint32_t *left, *right;
+    uint8_t *node_hash;
+};
+hipError_t cvk_pmt_build(uint32_t ntx, const CvkPmtBuild *a, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

@@ -22,6 +22,9 @@ CV_SIG_OK = 0
 CV_SIG_BAD_KEY = 1
 CV_TX_OK = 0
 CV_TX_EMPTY = 1
+CV_PMT_OK = 0
+CV_PMT_EMPTY = 1
+CV_PMT_NOT_IN_TREE = 3
 
 # every symbol include/cordaverify.h declares (tests check the library exports all of them)
 EXPORTED = (
@@ -35,7 +38,7 @@ EXPORTED = (
     "cv_verify_transactions", "cv_verify_transactions_async", "cv_open_ex", "cv_msg_extent",
     "cv_ed25519_verify_batch_ex", "cv_merkle_tx_ids_bounded", "cv_verify_transactions_ex",
     "cv_signer_open", "cv_signer_public_key", "cv_signer_close", "cv_ed25519_sign_keyed",
-    "cv_ed25519_sign_keyed_device",
+    "cv_ed25519_sign_keyed_device", "cv_partial_merkle_build_bound", "cv_partial_merkle_build", "cv_filtered_build",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -118,6 +121,13 @@ def load():
         lib.cv_partial_merkle_verify.argtypes = [_vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]
         lib.cv_partial_merkle_verify.restype = ctypes.c_int
         lib.cv_merkle_tx_ids_ex.restype = ctypes.c_int
+        lib.cv_partial_merkle_build_bound.argtypes = [_sz, _vp]
+        lib.cv_partial_merkle_build_bound.restype = ctypes.c_uint64
+        lib.cv_partial_merkle_build.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _sz] + [_vp] * 7 + [ctypes.POINTER(_sz)]
+        lib.cv_partial_merkle_build.restype = ctypes.c_int
+        lib.cv_filtered_build.argtypes = [_vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _sz] + [_vp] * 7 + \
+            [ctypes.POINTER(_sz)]
+        lib.cv_filtered_build.restype = ctypes.c_int
         lib.cv_ed25519_sign_batch.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.cv_ed25519_sign_batch.restype = ctypes.c_int
         lib.cv_ed25519_verify_batch_async.argtypes = [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -526,6 +536,65 @@ class Engine:
                "cv_partial_merkle_verify")
         return verdict[:ntrees], status[:ntrees]
 
+    def _build_out(self, ntx: int, tx_leaf_begin: np.ndarray, nodes_cap: Optional[int]):
+        cap = partial_merkle_build_bound(tx_leaf_begin) if nodes_cap is None else int(nodes_cap)
+        m = max(cap, 1)
+        return cap, (np.zeros(m, np.uint8), np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros((m, 32), np.uint8),
+                     np.zeros(ntx + 1, np.uint32), np.zeros((max(ntx, 1), 32), np.uint8), np.zeros(max(ntx, 1), np.uint8))
+
+    @staticmethod
+    def _build_result(rc: int, what: str, ntx: int, cap: int, out, nn: int):
+        """The node arrays cut to the nodes written; CV_E_ARGS from a short nodes_cap as ValueError with the count."""
+        kind, left, right, hashes, tb, ids, st = out
+        if rc == -3 and nn > cap:
+            raise ValueError(f"{what}: the batch needs {nn} nodes, nodes_cap is {cap}")
+        _check(rc, what)
+        return kind[:nn], left[:nn], right[:nn], hashes[:nn], tb, ids[:ntx], st[:ntx]
+
+    def partial_merkle_build(self, leaf_hash, tx_leaf_begin, include, include_begin, nodes_cap: Optional[int] = None):
+        """cv_partial_merkle_build: PartialMerkleTree.build for every transaction, leaf_hash (nleaves,32) u8 and
+        include (ninclude,32) u8 cut by tx_leaf_begin / include_begin (ntx+1 each) -> (kind, left, right,
+        node_hash (nnodes,32), tree_begin u32[ntx+1], ids (ntx,32), status u8[ntx]): the first five are
+        partial_merkle_verify's inputs as they stand.  nodes_cap: the node arrays' capacity (default: the bound)."""
+        tx_leaf_begin = np.ascontiguousarray(tx_leaf_begin, dtype=np.uint32)
+        include_begin = np.ascontiguousarray(include_begin, dtype=np.uint32)
+        ntx = tx_leaf_begin.shape[0] - 1
+        if ntx < 0 or include_begin.shape[0] != ntx + 1:
+            raise ValueError("tx_leaf_begin and include_begin must have ntx + 1 entries")
+        leaf_hash = _u8(leaf_hash)
+        include = _u8(include)
+        if ntx and (leaf_hash.size < 32 * int(tx_leaf_begin[-1]) or include.size < 32 * int(include_begin[-1])):
+            raise ValueError("the ranges reach past leaf_hash / include")
+        if leaf_hash.size == 0:
+            leaf_hash = np.zeros(32, np.uint8)
+        if include.size == 0:
+            include = np.zeros(32, np.uint8)
+        cap, out = self._build_out(ntx, tx_leaf_begin, nodes_cap)
+        nn = _sz(0)
+        rc = self._lib.cv_partial_merkle_build(self._h, ntx, _p(leaf_hash), _p(tx_leaf_begin), _p(include),
+                                               _p(include_begin), cap, *[_p(a) for a in out], ctypes.byref(nn))
+        return self._build_result(rc, "cv_partial_merkle_build", ntx, cap, out, nn.value)
+
+    def filtered_build(self, arena, leaf_off, leaf_len, tx_leaf_begin, keep, nodes_cap: Optional[int] = None):
+        """cv_filtered_build: FilteredTransaction.buildMerkleTransaction's trees for every transaction, the leaf
+        blobs as merkle_tx_ids takes them and keep u8[nleaves] (non-zero: the filters keep the leaf) -> as
+        partial_merkle_build (ids = the transactions' ids)."""
+        ntx, arena, leaf_off, leaf_len, tx_leaf_begin = self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
+        if ntx < 0:
+            raise ValueError("tx_leaf_begin must have ntx + 1 entries")
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if ntx and keep.shape[0] < int(tx_leaf_begin[-1]):
+            raise ValueError("keep must have one entry per leaf")
+        if keep.size == 0:
+            keep = np.zeros(1, np.uint8)
+        cap, out = self._build_out(ntx, tx_leaf_begin, nodes_cap)
+        nn = _sz(0)
+        rc = self._lib.cv_filtered_build(self._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len),
+                                         _p(tx_leaf_begin), _p(keep), cap, *[_p(a) for a in out], ctypes.byref(nn))
+        if rc == -3 and nn.value <= cap:
+            self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
+        return self._build_result(rc, "cv_filtered_build", ntx, cap, out, nn.value)
+
     # ------------------------------------------------------------ device-resident API
     def verify_device(self, device: int, n: int, d_pk: int, d_sig: int, d_arena: int, d_off: int, d_len: int,
                       d_bitmap: int, d_status: int = 0, stream: int = 0):
@@ -668,6 +737,14 @@ def tx_verdicts(bitmap: np.ndarray, tx_sig_begin) -> np.ndarray:
         bitmap = np.zeros(1, np.uint64)
     _check(lib.cv_tx_verdicts(ntx, _p(bitmap), _p(tx_sig_begin), _p(out)), "cv_tx_verdicts")
     return out
+
+
+def partial_merkle_build_bound(tx_leaf_begin) -> int:
+    """cv_partial_merkle_build_bound: the most nodes the builds of these transactions can emit (host only)."""
+    lib = load()
+    tx_leaf_begin = np.ascontiguousarray(tx_leaf_begin, dtype=np.uint32)
+    ntx = tx_leaf_begin.shape[0] - 1
+    return int(lib.cv_partial_merkle_build_bound(ntx, _p(tx_leaf_begin))) if ntx > 0 else 0
 
 
 def bitmap_to_bools(bitmap: np.ndarray, n: int) -> np.ndarray:

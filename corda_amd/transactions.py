@@ -271,7 +271,8 @@ def verify_signatures_batch_fused(stxs: Sequence[SignedTransaction], allowed_to_
 # ---------------------------------------------------------------- filtered transactions
 # Prover side (host): the full MerkleTree with its DuplicatedLeaf marks and PartialMerkleTree.build
 # (MerkleTransaction.kt:49-101, PartialMerkleTree.kt:69-111) — object work the JVM does once per
-# tear-off.  Verifier side (GPU): PartialMerkleTree.verify for many trees in one call
+# tear-off; build_partial_trees / build_filtered_batch below do the same for a whole batch on the GPU
+# (cv_partial_merkle_build, cv_filtered_build).  Verifier side (GPU): PartialMerkleTree.verify for many trees in one call
 # (cv_partial_merkle_verify), the root recompute + multiset check of PartialMerkleTree.kt:117-144.
 def _hash_concat(a: bytes, b: bytes) -> bytes:
     import hashlib
@@ -358,10 +359,63 @@ class PartialMerkleTree:
         rec(self.root)
         return kind, left, right, hashes
 
+    @staticmethod
+    def unflatten(kind, left, right, hashes, b: int, e: int) -> "PartialMerkleTree":
+        """The tree of nodes [b, e) of a flat encoding (flatten's inverse; cv_partial_merkle_build's output)."""
+        if e <= b:
+            raise IllegalArgumentException("malformed partial Merkle tree encoding")
+        nodes: Dict[int, PartialTree] = {}
+        for k in range(b, e):
+            if kind[k] == PartialMerkleTree.NODE:
+                nodes[k] = PartialTree(left=nodes[int(left[k])], right=nodes[int(right[k])])
+            else:
+                nodes[k] = PartialTree(SecureHash(bytes(hashes[k])), included=kind[k] == PartialMerkleTree.INCLUDED)
+        return PartialMerkleTree(nodes[e - 1])
+
     def verify(self, merkle_root_hash: SecureHash, hashes_to_check: Sequence[SecureHash],
                engine: Optional[native.Engine] = None) -> bool:
         """PartialMerkleTree.verify (PartialMerkleTree.kt:117-124), on the GPU."""
         return verify_partial_trees([(self, merkle_root_hash, list(hashes_to_check))], engine)[0]
+
+
+_BUILD_ERRORS = {native.CV_PMT_EMPTY: "Cannot calculate Merkle root on empty hash list.",
+                 native.CV_PMT_NOT_IN_TREE: "Some of the provided hashes are not in the tree."}
+
+
+def _trees_of(out, raise_first: bool) -> list:
+    """The PartialMerkleTree (or MerkleTreeException) of every transaction of a build call's output."""
+    kind, left, right, hashes, tb, _, st = out
+    res: list = []
+    for t in range(len(st)):
+        if st[t] != native.CV_PMT_OK:
+            err = MerkleTreeException(_BUILD_ERRORS[int(st[t])])
+            if raise_first:
+                raise err
+            res.append(err)
+        else:
+            res.append(PartialMerkleTree.unflatten(kind, left, right, hashes, int(tb[t]), int(tb[t + 1])))
+    return res
+
+
+def build_partial_trees(items, engine: Optional[native.Engine] = None, raise_first: bool = True) -> list:
+    """Many PartialMerkleTree.build(MerkleTree.getMerkleTree(leafHashes), includeHashes) in ONE GPU call
+    (cv_partial_merkle_build).  items: (leaf_hashes, include_hashes), SecureHash sequences.  Returns the
+    PartialMerkleTrees; the first failing item raises the reference's MerkleTreeException as the sequential
+    loop would — or, with raise_first=False, the exception stands in the list in the item's place."""
+    leaves: List[bytes] = []
+    incl: List[bytes] = []
+    lb, ib = [0], [0]
+    for lh, inc in items:
+        leaves += [h.bytes for h in lh]
+        incl += [h.bytes for h in inc]
+        lb.append(len(leaves))
+        ib.append(len(incl))
+    if not items:
+        return []
+    eng = engine or native.default_engine()
+    as_rows = lambda bs: np.frombuffer(b"".join(bs), np.uint8).reshape(-1, 32)  # noqa: E731
+    out = eng.partial_merkle_build(as_rows(leaves), np.array(lb, np.uint32), as_rows(incl), np.array(ib, np.uint32))
+    return _trees_of(out, raise_first)
 
 
 def verify_partial_trees(items, engine: Optional[native.Engine] = None) -> List[bool]:
@@ -440,3 +494,44 @@ def verify_filtered_batch(items, engine: Optional[native.Engine] = None) -> List
             raise MerkleTreeException("Transaction without included leaves.")
         batch.append((ftx.partial_merkle_tree, root, hashes))
     return verify_partial_trees(batch, engine)
+
+
+def build_filtered_batch(wtxs: Sequence[WireTransaction], filters, engine: Optional[native.Engine] = None,
+                         raise_first: bool = True):
+    """FilteredTransaction.buildMerkleTransaction for many transactions in ONE GPU call (cv_filtered_build: leaf
+    hashes, full trees and pruned trees on the device).  filters: (filter_inputs, filter_outputs,
+    filter_attachments, filter_commands) — FilterFuns over the serialized leaves, None = keep nothing of that
+    group — for all transactions, or one such tuple per transaction.  Returns (FilteredTransactions, ids): ids[k] =
+    the transaction's SecureHash id, None for a transaction without leaves.  Failures as build_partial_trees."""
+    if not wtxs:
+        return [], []
+    per_tx = len(filters) == len(wtxs) and all(isinstance(f, (tuple, list)) for f in filters)
+    leaves: List[bytes] = []
+    keep: List[int] = []
+    begin = [0]
+    kept_leaves = []
+    for k, wtx in enumerate(wtxs):
+        fi, fo, fa, fc = [f or (lambda b: False) for f in (filters[k] if per_tx else filters)]
+        fl = FilteredLeaves([x for x in wtx.inputs if fi(x)], [x for x in wtx.outputs if fo(x)],
+                            [x for x in wtx.attachments if fa(x)], [x for x in wtx.commands if fc(x)])
+        kept_leaves.append(fl)
+        for group, f in ((wtx.inputs, fi), (wtx.outputs, fo), (wtx.attachments, fa), (wtx.commands, fc)):
+            leaves.extend(group)
+            keep.extend(1 if f(x) else 0 for x in group)
+        begin.append(len(leaves))
+    lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
+    offs = np.zeros(len(leaves), np.uint64)
+    if len(leaves) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+    eng = engine or native.default_engine()
+    out = eng.filtered_build(arena, offs, lens, np.array(begin, np.uint32), np.array(keep, np.uint8))
+    ids: List[Optional[SecureHash]] = []
+    for k, wtx in enumerate(wtxs):
+        if out[6][k] == native.CV_PMT_EMPTY:
+            ids.append(None)
+        else:
+            wtx._id = SecureHash(out[5][k].tobytes())
+            ids.append(wtx._id)
+    trees = _trees_of(out, raise_first)
+    return [t if isinstance(t, Exception) else FilteredTransaction(fl, t) for fl, t in zip(kept_leaves, trees)], ids

@@ -34,6 +34,10 @@
  *                                 core/src/main/kotlin/net/corda/core/crypto/PartialMerkleTree.kt:117-144
  *                             behind FilteredTransaction.verify (MerkleTransaction.kt:170-178; the
  *                             oracle tear-off check of NodeInterestRates.kt:189-191)
+ *   cv_partial_merkle_build   N x  PartialMerkleTree.build(merkleRoot, includeHashes)
+ *                                 PartialMerkleTree.kt:69-111 over MerkleTree.getMerkleTree (MerkleTransaction.kt:66-99)
+ *   cv_filtered_build         N x  FilteredTransaction.buildMerkleTransaction (MerkleTransaction.kt:146-168): leaf
+ *                                 hashes, full tree and pruned tree of every tear-off in one call
  *
  * Conventions
  *   - Return codes: CV_OK (0) or a negative CV_E* code; nothing throws, aborts or longjmps across
@@ -203,6 +207,52 @@ int cv_partial_merkle_verify(cv_ctx *ctx, size_t ntrees, size_t nnodes, const ui
                              size_t ncheck, const uint8_t *check /* ncheck*32 */,
                              const uint32_t *check_begin /* ntrees+1 */, uint8_t *verdict /* ntrees */,
                              uint8_t *status /* ntrees, optional */);
+
+/* Partial Merkle tree BUILD (tear-offs, the prover side): for every transaction the full tree of
+ * MerkleTree.getMerkleTree (MerkleTransaction.kt:66-99: a level's odd last node gets a DuplicatedLeaf with its own
+ * hash as right sibling) pruned by PartialMerkleTree.build (PartialMerkleTree.kt:69-111), written in the flat
+ * encoding cv_partial_merkle_verify reads, so a build's outputs are a verify's inputs as they stand.
+ *   - A leaf becomes an IncludedLeaf iff its hash occurs in the include list (by hash, not position; a
+ *     DuplicatedLeaf never); a node above an IncludedLeaf becomes a Node (32 zero bytes in node_hash), every other
+ *     subtree is cut to a Leaf with its hash; for leaves left = right = 0.
+ *   - status[t]: CV_PMT_OK; CV_PMT_EMPTY for no leaves; CV_PMT_NOT_IN_TREE iff the number of IncludedLeaves differs
+ *     from the include list's length (an absent hash, a hash listed twice for one leaf, a listed hash that several
+ *     leaves carry) — the reference's MerkleTreeException messages.  An empty include list is legal: one Leaf(root).
+ *   - tree_begin[ntx+1]: transaction t's nodes are [tree_begin[t], tree_begin[t+1]), root last; a transaction whose
+ *     status is not CV_PMT_OK has none.  *nnodes = tree_begin[ntx].
+ *   - ids[t][32] (optional): the Merkle root (WireTransaction.id) of every transaction with a leaf, zero bytes for
+ *     CV_PMT_EMPTY.
+ *   - nodes_cap: the capacity of kind / left / right / node_hash in nodes.  If the batch needs more, the call
+ *     writes tree_begin, status, ids and *nnodes, leaves the node arrays alone and returns CV_E_ARGS; a caller
+ *     that allocates cv_partial_merkle_build_bound nodes never sees this.
+ * Synchronous, on one device (the least loaded).  Ranges as cv_partial_merkle_verify: begin[0] == 0, monotone
+ * (CV_E_ARGS otherwise); more than 0xfffffffe transactions, leaves, include hashes or nodes of the bound:
+ * CV_E_TOO_LARGE.  ntx == 0 returns CV_OK and touches nothing. */
+#define CV_PMT_EMPTY 1          /* no leaves: MerkleTreeException("Cannot calculate Merkle root on empty hash list.") */
+#define CV_PMT_NOT_IN_TREE 3    /* MerkleTreeException("Some of the provided hashes are not in the tree.") */
+
+/* host only: the sum over the transactions of the most nodes a build can emit (all leaves included) — for L leaves
+ * the entries of all levels plus one per level with an odd count above 1 (13 for L = 5, 141 for L = 65) */
+uint64_t cv_partial_merkle_build_bound(size_t ntx, const uint32_t *tx_leaf_begin /* ntx+1 */);
+
+/* N x PartialMerkleTree.build(MerkleTree.getMerkleTree(leafHashes), includeHashes)  (PartialMerkleTree.kt:69-111) */
+int cv_partial_merkle_build(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_hash /* nleaves*32 */,
+                            const uint32_t *tx_leaf_begin /* ntx+1 */, const uint8_t *include /* ninclude*32 */,
+                            const uint32_t *include_begin /* ntx+1 */, size_t nodes_cap, uint8_t *kind, uint32_t *left,
+                            uint32_t *right, uint8_t *node_hash /* nodes_cap*32 */, uint32_t *tree_begin /* ntx+1 */,
+                            uint8_t *ids /* ntx*32, optional */, uint8_t *status /* ntx */, size_t *nnodes);
+
+/* N x FilteredTransaction.buildMerkleTransaction (MerkleTransaction.kt:146-168; caller RatesFixFlow.kt:100-110): the
+ * leaf blobs as cv_merkle_tx_ids_bounded takes them (hashed by the same leaf kernel; leaves past
+ * leaf_arena[leaf_arena_bytes) or wrapping give CV_E_ARGS before any read), keep[nleaves] = the FilterFuns' verdict
+ * per leaf (non-zero: kept).  The include list of a transaction is the hashes of its kept leaves, so a leaf is
+ * included iff its hash equals a kept leaf's, and a kept leaf whose bytes another leaf repeats gives
+ * CV_PMT_NOT_IN_TREE as in the reference.  Outputs as cv_partial_merkle_build. */
+int cv_filtered_build(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_t leaf_arena_bytes,
+                      const uint64_t *leaf_off, const uint32_t *leaf_len, const uint32_t *tx_leaf_begin /* ntx+1 */,
+                      const uint8_t *keep /* nleaves */, size_t nodes_cap, uint8_t *kind, uint32_t *left,
+                      uint32_t *right, uint8_t *node_hash /* nodes_cap*32 */, uint32_t *tree_begin /* ntx+1 */,
+                      uint8_t *ids /* ntx*32, optional */, uint8_t *status /* ntx */, size_t *nnodes);
 
 int cv_ed25519_sign_batch(cv_ctx *ctx, size_t n, const uint8_t *seed /* n*32 */, const uint8_t *msg_arena,
                           const uint64_t *msg_off, const uint32_t *msg_len, uint8_t *pk_out /* n*32 */,
