@@ -7,6 +7,7 @@
 //   cv_k_misc.hip  signing (synthetic inputs), Merkle ids, partial Merkle trees, calibration kernels
 //   cv_k_sign.hip  fixed-key signing (signer key expansion, one signature per lane)
 //   cv_k_pmt.hip   partial Merkle tree build (tear-offs): count, scan, emit
+//   cv_k_uniq.hip  the notary's uniqueness set (cv_uniq.h): group, rounds, tail, report + insert, load, lookup, rehash
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 #include "cv_verify.h"
 #include "cv_quad.h"
 #include "cv_hsquad.h"
+#include "cv_uniq.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -162,6 +164,18 @@ __global__ void cv_pmt_verify_kernel(uint32_t ntrees, const uint8_t *kind, const
 __global__ void cv_pmt_count_kernel(uint32_t ntx, const uint8_t *leaf_hash, const uint32_t *leaf_dig, const uint32_t *tx_leaf_begin, const uint8_t *include, const uint32_t *include_begin, const uint8_t *keep, const uint32_t *ws_off, uint32_t *dig, uint8_t *flag, uint32_t *size, uint32_t *pos, uint8_t *ids, uint8_t *status, uint32_t *count);
 __global__ void cv_pmt_scan_kernel(uint32_t n, const uint32_t *count, uint32_t *tree_begin);
 __global__ void cv_pmt_emit_kernel(uint32_t ntx, const uint32_t *tx_leaf_begin, const uint32_t *ws_off, const uint32_t *dig, const uint8_t *flag, const uint32_t *size, uint32_t *pos, const uint8_t *status, const uint32_t *tree_begin, uint8_t *kind, uint32_t *left, uint32_t *right, uint8_t *node_hash);
+// the uniqueness set (cv_k_uniq.hip, cv_uniq.h): one lane per request or per state; the tail is one wave
+__global__ void cv_uniq_init_kernel(CvUniqBatch B, uint32_t *stat);
+__global__ void cv_uniq_group_kernel(CvUniqTable T, CvUniqBatch B, uint32_t *stat);
+__global__ void cv_uniq_claim_kernel(CvUniqBatch B, const uint32_t *stat);
+__global__ void cv_uniq_decide_kernel(CvUniqBatch B, const uint32_t *stat_in, uint32_t *stat_out, uint32_t *undecided);
+__global__ void cv_uniq_own_kernel(CvUniqBatch B, const uint32_t *stat);
+__global__ void cv_uniq_tail_kernel(CvUniqBatch B, uint32_t *stat);
+__global__ void cv_uniq_report_kernel(CvUniqTable T, CvUniqBatch B, const uint32_t *stat);
+__global__ void cv_uniq_load_check_kernel(CvUniqBatch B);
+__global__ void cv_uniq_load_put_kernel(CvUniqTable T, CvUniqBatch B);
+__global__ void cv_uniq_lookup_kernel(CvUniqTable T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id, uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat);
+__global__ void cv_uniq_rehash_kernel(CvUniqTable from, CvUniqTable to, uint32_t *dstat);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

@@ -335,6 +335,77 @@ hipError_t cvk_pmt_build(uint32_t ntx, const CvkPmtBuild *a, hipStream_t stream)
     return hipGetLastError();
 }
 
+// ---- the uniqueness set (cv_uniq.h).  Grids of one lane per request / state / slot; counts are below 2^31.
+static dim3 uniq_grid(uint64_t n) { return dim3((unsigned)((n + CV_BLOCK - 1) / CV_BLOCK)); }
+
+hipError_t cvk_uniq_front(const CvUniqTable *T, const CvUniqBatch *B, uint32_t *stat, hipStream_t stream) {
+    if (!T || !B || !stat || B->ntx == 0) return hipErrorInvalidValue;
+    const dim3 block(CV_BLOCK);
+    hipLaunchKernelGGL(cv_uniq_init_kernel, uniq_grid(B->ntx), block, 0, stream, *B, stat);
+    if (B->nstates) {
+        hipError_t e = hipMemsetAsync(B->btab, 0xff, 4 * ((size_t)B->bmask + 1), stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cv_uniq_group_kernel, uniq_grid(B->nstates), block, 0, stream, *T, *B, stat);
+    }
+    return hipGetLastError();
+}
+
+hipError_t cvk_uniq_round(const CvUniqBatch *B, const uint32_t *stat_in, uint32_t *stat_out, uint32_t round,
+                          hipStream_t stream) {
+    if (!B || B->ntx == 0 || round >= CVU_MAX_ROUNDS) return hipErrorInvalidValue;
+    const dim3 grid = uniq_grid(B->ntx), block(CV_BLOCK);
+    if (B->nstates) {
+        hipError_t e = hipMemsetAsync(B->owner, 0xff, 4 * (size_t)B->nstates, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cv_uniq_claim_kernel, grid, block, 0, stream, *B, stat_in);
+    }
+    hipLaunchKernelGGL(cv_uniq_decide_kernel, grid, block, 0, stream, *B, stat_in, stat_out,
+                       B->dstat + CVU_D_ROUND0 + round);
+    return hipGetLastError();
+}
+
+hipError_t cvk_uniq_finish(const CvUniqTable *T, const CvUniqBatch *B, uint32_t *stat, int tail, hipStream_t stream) {
+    if (!T || !B || B->ntx == 0) return hipErrorInvalidValue;
+    const dim3 grid = uniq_grid(B->ntx), block(CV_BLOCK);
+    if (B->nstates) {
+        hipError_t e = hipMemsetAsync(B->owner, 0xff, 4 * (size_t)B->nstates, stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cv_uniq_own_kernel, grid, block, 0, stream, *B, stat);
+    }
+    if (tail) hipLaunchKernelGGL(cv_uniq_tail_kernel, dim3(1), dim3(64), 0, stream, *B, stat);
+    hipLaunchKernelGGL(cv_uniq_report_kernel, grid, block, 0, stream, *T, *B, stat);
+    return hipGetLastError();
+}
+
+hipError_t cvk_uniq_load(const CvUniqTable *T, const CvUniqBatch *B, int phase, hipStream_t stream) {
+    if (!T || !B || B->nstates == 0) return hipErrorInvalidValue;
+    const dim3 grid = uniq_grid(B->nstates), block(CV_BLOCK);
+    if (phase == 0) {
+        hipError_t e = hipMemsetAsync(B->btab, 0xff, 4 * ((size_t)B->bmask + 1), stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cv_uniq_group_kernel, grid, block, 0, stream, *T, *B, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(cv_uniq_load_check_kernel, grid, block, 0, stream, *B);
+    } else {
+        hipLaunchKernelGGL(cv_uniq_load_put_kernel, grid, block, 0, stream, *T, *B);
+    }
+    return hipGetLastError();
+}
+
+hipError_t cvk_uniq_lookup(const CvUniqTable *T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id,
+                           uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat, hipStream_t stream) {
+    if (!T || n == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_uniq_lookup_kernel, uniq_grid(n), dim3(CV_BLOCK), 0, stream, *T, n, key, found, cons_id,
+                       cons_index, cons_caller, dstat);
+    return hipGetLastError();
+}
+
+hipError_t cvk_uniq_rehash(const CvUniqTable *from, const CvUniqTable *to, uint32_t *dstat, hipStream_t stream) {
+    if (!from || !to) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_uniq_rehash_kernel, uniq_grid((uint64_t)from->mask + 1), dim3(CV_BLOCK), 0, stream, *from, *to,
+                       dstat);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cv_uniq.h"
+
 // Helper stream and events of one verify workspace slot, used by cvk_verify's drain overlap (a
 // near-empty last round of a chunk is filled by a tail sub-chunk on s2).  Owned by cv_api.cpp (one per
 // workspace slot, so two slots' calls never share a helper stream); cvk_verify only records and waits.
@@ -75,6 +77,22 @@ struct CvkPmtBuild {
     uint8_t *node_hash;
 };
 hipError_t cvk_pmt_build(uint32_t ntx, const CvkPmtBuild *a, hipStream_t stream);
+// The uniqueness set (cv_uniq.h; kernels in cv_k_uniq.hip), every step enqueued on `stream`, nothing synchronised.
+//   front : clears the batch table, then init (per request) and group + resident lookup (per state) into stat
+//   round : owner = none, claim, decide stat_in -> stat_out; the requests still undecided are added to
+//           dstat[CVU_D_ROUND0 + round] (zero before)
+//   finish: owner = none, own, the one-wave serial tail when `tail` is set, report + insert
+//   load  : phase 0 clears the batch table, groups the keys and looks them up (dstat[CVU_D_BAD] if one repeats or
+//           is resident); phase 1 inserts them
+//   rehash: one lane per slot of `from` re-inserts into `to` (occ of `to` zero before)
+hipError_t cvk_uniq_front(const CvUniqTable *T, const CvUniqBatch *B, uint32_t *stat, hipStream_t stream);
+hipError_t cvk_uniq_round(const CvUniqBatch *B, const uint32_t *stat_in, uint32_t *stat_out, uint32_t round,
+                          hipStream_t stream);
+hipError_t cvk_uniq_finish(const CvUniqTable *T, const CvUniqBatch *B, uint32_t *stat, int tail, hipStream_t stream);
+hipError_t cvk_uniq_load(const CvUniqTable *T, const CvUniqBatch *B, int phase, hipStream_t stream);
+hipError_t cvk_uniq_lookup(const CvUniqTable *T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id,
+                           uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat, hipStream_t stream);
+hipError_t cvk_uniq_rehash(const CvUniqTable *from, const CvUniqTable *to, uint32_t *dstat, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

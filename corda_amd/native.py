@@ -25,6 +25,10 @@ CV_TX_EMPTY = 1
 CV_PMT_OK = 0
 CV_PMT_EMPTY = 1
 CV_PMT_NOT_IN_TREE = 3
+CV_UNIQ_OK = 0
+CV_UNIQ_CONFLICT = 1
+CV_UNIQ_SKIPPED = 2
+CV_UNIQ_STATS = ("resident", "capacity", "slots", "rounds", "tail", "probe", "wraps")   # CV_UNIQ_STAT_*
 
 # every symbol include/cordaverify.h declares (tests check the library exports all of them)
 EXPORTED = (
@@ -39,6 +43,8 @@ EXPORTED = (
     "cv_ed25519_verify_batch_ex", "cv_merkle_tx_ids_bounded", "cv_verify_transactions_ex",
     "cv_signer_open", "cv_signer_public_key", "cv_signer_close", "cv_ed25519_sign_keyed",
     "cv_ed25519_sign_keyed_device", "cv_partial_merkle_build_bound", "cv_partial_merkle_build", "cv_filtered_build",
+    "cv_uniq_open", "cv_uniq_close", "cv_uniq_reserve", "cv_uniq_commit_batch", "cv_uniq_lookup", "cv_uniq_load",
+    "cv_uniq_set_max_rounds", "cv_uniq_stats",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -159,6 +165,22 @@ def load():
         lib.cv_signer_public_key.restype = ctypes.c_int
         lib.cv_signer_close.argtypes = [_vp]
         lib.cv_signer_close.restype = None
+        lib.cv_uniq_open.argtypes = [_vp, ctypes.c_int, _sz, ctypes.POINTER(_vp)]
+        lib.cv_uniq_open.restype = ctypes.c_int
+        lib.cv_uniq_close.argtypes = [_vp]
+        lib.cv_uniq_close.restype = None
+        lib.cv_uniq_reserve.argtypes = [_vp, _sz]
+        lib.cv_uniq_reserve.restype = ctypes.c_int
+        lib.cv_uniq_commit_batch.argtypes = [_vp, _sz] + [_vp] * 10
+        lib.cv_uniq_commit_batch.restype = ctypes.c_int
+        lib.cv_uniq_lookup.argtypes = [_vp, _sz] + [_vp] * 5
+        lib.cv_uniq_lookup.restype = ctypes.c_int
+        lib.cv_uniq_load.argtypes = [_vp, _sz] + [_vp] * 4
+        lib.cv_uniq_load.restype = ctypes.c_int
+        lib.cv_uniq_set_max_rounds.argtypes = [_vp, ctypes.c_int]
+        lib.cv_uniq_set_max_rounds.restype = ctypes.c_int
+        lib.cv_uniq_stats.argtypes = [_vp, _vp, _sz]
+        lib.cv_uniq_stats.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp]
         lib.cv_ed25519_sign_keyed.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed_device.argtypes = [_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -253,7 +275,7 @@ class Engine:
         self._h = h
         self.mu = threading.Lock()
         self._inflight = {}
-        self._signers = weakref.WeakSet()   # open Signer objects: a signer is closed before its context
+        self._signers = weakref.WeakSet()   # open Signer and UniquenessSet objects: closed before their context
 
     def close(self):
         if self._h:
@@ -711,6 +733,114 @@ class Signer:
             raise ValueError("the signer is closed")
         _check(self._lib.cv_ed25519_sign_keyed_device(self._engine._h, device, self._h, n, d_arena, d_off, d_len,
                                                       d_sig, stream or None), "cv_ed25519_sign_keyed_device")
+
+
+class UniquenessSet:
+    """A device-resident set of consumed states bound to an engine (cv_uniq): the notary's commit step,
+    UniquenessProvider.commit (UniquenessProvider.kt:13-35) as InMemoryUniquenessProvider.kt:14-36 decides it, for
+    a whole batch in one call.  Keys are 32 bytes, a consuming record is (tx id[32], input index u32, caller u32).
+    Calls serialise on the set's own lock.  close() (or the with-statement) frees the table; the engine closes the
+    sets still open when it is closed itself."""
+
+    def __init__(self, engine: Engine, capacity: int, device: int = 0):
+        self._engine = engine
+        self._lib = engine._lib
+        h = _vp()
+        _check(self._lib.cv_uniq_open(engine._h, device, int(capacity), ctypes.byref(h)), "cv_uniq_open")
+        self._h = h
+        engine._signers.add(self)
+
+    def close(self):
+        if self._h:
+            self._lib.cv_uniq_close(self._h)
+            self._h = None
+            self._engine._signers.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("the uniqueness set is closed")
+        return self._h
+
+    def commit_batch(self, state_key, tx_state_begin, tx_id, caller, tx_enable=None, out=None):
+        """cv_uniq_commit_batch: state_key (nstates,32) u8 cut by tx_state_begin u32[ntx+1], tx_id (ntx,32) u8,
+        caller u32[ntx], tx_enable u8[ntx] or None -> (tx_status u8[ntx], state_conflict u8[nstates], consumed_id
+        (nstates,32) u8, consumed_index u32[nstates], consumed_caller u32[nstates]), decided as ntx sequential
+        commits.  CvError with code -4 when the set would pass its capacity: nothing changed, reserve() first.
+        out: the five output arrays to write into (default: fresh ones)."""
+        h = self._open()
+        tx_state_begin = np.ascontiguousarray(tx_state_begin, dtype=np.uint32)
+        ntx = tx_state_begin.shape[0] - 1
+        if ntx < 0:
+            raise ValueError("tx_state_begin must have ntx + 1 entries")
+        ns = int(tx_state_begin[-1])
+        state_key = _u8(state_key)
+        tx_id = _u8(tx_id)
+        caller = np.ascontiguousarray(caller, dtype=np.uint32)
+        if state_key.size < 32 * ns or tx_id.size < 32 * ntx or caller.shape[0] < ntx:
+            raise ValueError("the ranges reach past state_key / tx_id / caller")
+        if tx_enable is not None:
+            tx_enable = np.ascontiguousarray(tx_enable, dtype=np.uint8)
+            if tx_enable.shape[0] < ntx:
+                raise ValueError("tx_enable must have one entry per request")
+        if state_key.size == 0:
+            state_key = np.zeros(32, np.uint8)
+        if out is None:
+            m = max(ns, 1)
+            out = (np.zeros(max(ntx, 1), np.uint8), np.zeros(m, np.uint8), np.zeros((m, 32), np.uint8),
+                   np.zeros(m, np.uint32), np.zeros(m, np.uint32))
+        _check(self._lib.cv_uniq_commit_batch(h, ntx, _p(state_key), _p(tx_state_begin), _p(tx_id), _p(caller),
+                                              _p(tx_enable), *[_p(a) for a in out]), "cv_uniq_commit_batch")
+        st, sc, cid, cix, cc = out
+        return st[:ntx], sc[:ns], cid[:ns], cix[:ns], cc[:ns]
+
+    def lookup(self, state_key):
+        """cv_uniq_lookup: state_key (n,32) u8 -> (found u8[n], consumed_id (n,32), consumed_index, consumed_caller)."""
+        h = self._open()
+        state_key = _u8(state_key)
+        n = state_key.size // 32
+        m = max(n, 1)
+        found, cid = np.zeros(m, np.uint8), np.zeros((m, 32), np.uint8)
+        cix, cc = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        _check(self._lib.cv_uniq_lookup(h, n, _p(state_key), _p(found), _p(cid), _p(cix), _p(cc)), "cv_uniq_lookup")
+        return found[:n], cid[:n], cix[:n], cc[:n]
+
+    def load(self, state_key, consumed_id, consumed_index, consumed_caller):
+        """cv_uniq_load: n rows of a durable log into the set; CvError -3 (the set unchanged) if a key repeats in
+        the call or is resident, -4 past the capacity."""
+        h = self._open()
+        state_key = _u8(state_key)
+        consumed_id = _u8(consumed_id)
+        n = state_key.size // 32
+        consumed_index = np.ascontiguousarray(consumed_index, dtype=np.uint32)
+        consumed_caller = np.ascontiguousarray(consumed_caller, dtype=np.uint32)
+        if consumed_id.size != 32 * n or consumed_index.shape[0] != n or consumed_caller.shape[0] != n:
+            raise ValueError("one id, index and caller per key")
+        _check(self._lib.cv_uniq_load(h, n, _p(state_key), _p(consumed_id), _p(consumed_index), _p(consumed_caller)),
+               "cv_uniq_load")
+
+    def reserve(self, capacity: int):
+        _check(self._lib.cv_uniq_reserve(self._open(), int(capacity)), "cv_uniq_reserve")
+
+    def set_max_rounds(self, rounds: int):
+        _check(self._lib.cv_uniq_set_max_rounds(self._open(), int(rounds)), "cv_uniq_set_max_rounds")
+
+    def stats(self) -> dict:
+        """cv_uniq_stats (diagnostics): resident, capacity, slots, rounds and tail of the last commit, probe, wraps."""
+        out = np.zeros(len(CV_UNIQ_STATS), np.uint64)
+        _check(self._lib.cv_uniq_stats(self._open(), _p(out), out.shape[0]), "cv_uniq_stats")
+        return dict(zip(CV_UNIQ_STATS, (int(v) for v in out)))
 
 
 def dedupe_keys(pk: np.ndarray):

@@ -15,7 +15,8 @@ conflicts with states committed by an EARLIER request of the same batch, never a
 conflicting request commits nothing), but the persistent provider does it in ONE database
 transaction — one lock acquisition and one durable commit (fsync) per batch instead of per
 transaction.  Each result is None (committed) or the UniquenessConflict the sequential call would
-have raised.
+have raised.  DeviceUniquenessProvider makes the same decisions on the GPU: the device-resident set of
+include/cordaverify.h (cv_uniq), one call per batch, optionally with the persistent provider as its durable log.
 
 The node's JDBC/H2 store is out of scope; the persistent provider keeps the
 reference's table and columns on SQLite (Python's sqlite3, synchronous=FULL, WAL journal), keyed by
@@ -23,11 +24,14 @@ the canonical encoding of the state reference.
 """
 from __future__ import annotations
 
+import hashlib
 import sqlite3
 import struct
 import threading
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 from .crypto import IllegalArgumentException
 from .transactions import SecureHash
@@ -214,6 +218,117 @@ class PersistentUniquenessProvider:
                     except Exception:  # noqa: BLE001 - the original exception is the one to report
                         pass
                 raise
+        return out
+
+    def commit(self, states: Sequence[object], tx_id: SecureHash, caller: str) -> None:
+        (c,) = self.commit_batch([(states, tx_id, caller)])
+        if c is not None:
+            raise UniquenessException(c)
+
+
+class DeviceUniquenessProvider:
+    """The commit step on the device: a native.UniquenessSet (cv_uniq, include/cordaverify.h) behind the interface
+    of the two providers above.  A batch is decided in ONE call, exactly as InMemoryUniquenessProvider.commit_batch
+    decides it.
+
+    The set's key is sha256(_enc(state)) (the reference's choice would be SecureHash.sha256 of the serialised
+    StateRef, Structures.kt:337); party names map to u32 handles through a table kept here; a conflict comes back
+    as the UniquenessConflict the sequential call would have raised.  The set grows (reserve) when a batch would
+    pass its capacity.
+
+    The device set is not durable.  With log= a PersistentUniquenessProvider, the set is loaded from the log's rows
+    at start, and each batch's accepted rows are appended to the log in one durable transaction before the call
+    returns — no SELECT: the device has already decided.  If that append fails the error is raised and the provider
+    refuses further work: the set then holds states the log does not, and has to be rebuilt from the log."""
+
+    def __init__(self, engine, capacity: int = 1 << 16, log: Optional[PersistentUniquenessProvider] = None):
+        from . import native
+        self._lock = threading.Lock()
+        self._parties: List[str] = []
+        self._handle: Dict[str, int] = {}
+        self._log = log
+        self._broken = False
+        rows = []
+        if log is not None:
+            with log._lock:
+                rows = log._db.execute(f"SELECT output, consuming_transaction_id, consuming_input_index, "
+                                       f"requesting_party_name FROM {log.TABLE}").fetchall()
+        self._set = native.UniquenessSet(engine, max(int(capacity), 2 * len(rows), 1))
+        if rows:
+            self._set.load(np.frombuffer(b"".join(self._key(bytes(r[0])) for r in rows), np.uint8),
+                           np.frombuffer(b"".join(bytes(r[1]) for r in rows), np.uint8),
+                           np.array([int(r[2]) for r in rows], np.uint32),
+                           np.array([self._party(r[3]) for r in rows], np.uint32))
+
+    @staticmethod
+    def _key(enc: bytes) -> bytes:
+        return hashlib.sha256(enc).digest()
+
+    def _party(self, name: str) -> int:
+        h = self._handle.get(name)
+        if h is None:
+            h = self._handle[name] = len(self._parties)
+            self._parties.append(name)
+        return h
+
+    def close(self) -> None:
+        self._set.close()
+
+    def __len__(self) -> int:
+        return self._set.stats()["resident"]
+
+    def get(self, state) -> Optional[ConsumingTx]:
+        with self._lock:
+            found, cid, cix, cc = self._set.lookup(np.frombuffer(self._key(_enc(state)), np.uint8))
+            return ConsumingTx(SecureHash(cid[0].tobytes()), int(cix[0]), self._parties[int(cc[0])]) if found[0] else None
+
+    def commit_batch(self, requests: Sequence[CommitRequest]) -> List[Optional[UniquenessConflict]]:
+        if not requests:
+            return []
+        encs = [[_enc(s) for s in states] for states, _, _ in requests]
+        begin = np.zeros(len(requests) + 1, np.uint32)
+        np.cumsum([len(e) for e in encs], out=begin[1:])
+        ns = int(begin[-1])
+        keys = np.frombuffer(b"".join(self._key(e) for es in encs for e in es), np.uint8)
+        ids = np.frombuffer(b"".join(t.bytes for _, t, _ in requests), np.uint8)
+        with self._lock:
+            if self._broken:
+                raise RuntimeError("the device set is ahead of its log: rebuild it from the log")
+            callers = np.array([self._party(c) for _, _, c in requests], np.uint32)
+            st = self._set.stats()
+            if st["resident"] + ns > st["capacity"]:
+                self._set.reserve(max(2 * st["capacity"], st["resident"] + ns))
+            status, conflict, cid, cix, cc = self._set.commit_batch(keys, begin, ids, callers)
+            if self._log is not None:
+                rows = [(e, t.bytes, i, c) for (_, t, c), es, ok in zip(requests, encs, status == 0) if ok
+                        for i, e in enumerate(es)]
+                try:
+                    with self._log._lock:
+                        db = self._log._db
+                        db.execute("BEGIN IMMEDIATE")
+                        try:
+                            db.executemany(f"INSERT OR REPLACE INTO {self._log.TABLE} VALUES (?, ?, ?, ?)", rows)
+                            db.execute("COMMIT")
+                        except BaseException:
+                            if db.in_transaction:
+                                try:
+                                    db.execute("ROLLBACK")
+                                except Exception:  # noqa: BLE001 - the original exception is the one to report
+                                    pass
+                            raise
+                except BaseException:
+                    self._broken = True
+                    raise
+            parties = list(self._parties)
+        out: List[Optional[UniquenessConflict]] = []
+        for t, (states, _, _) in enumerate(requests):
+            if status[t] == 0:
+                out.append(None)
+                continue
+            b = int(begin[t])
+            out.append(UniquenessConflict({s: ConsumingTx(SecureHash(cid[b + j].tobytes()), int(cix[b + j]),
+                                                          parties[int(cc[b + j])])
+                                           for j, s in enumerate(states) if conflict[b + j]}))
         return out
 
     def commit(self, states: Sequence[object], tx_id: SecureHash, caller: str) -> None:

@@ -38,6 +38,11 @@
  *                                 PartialMerkleTree.kt:69-111 over MerkleTree.getMerkleTree (MerkleTransaction.kt:66-99)
  *   cv_filtered_build         N x  FilteredTransaction.buildMerkleTransaction (MerkleTransaction.kt:146-168): leaf
  *                                 hashes, full tree and pruned tree of every tear-off in one call
+ *   cv_uniq_open +            N x  UniquenessProvider.commit(states, txId, callerIdentity)
+ *   cv_uniq_commit_batch          core/src/main/kotlin/net/corda/core/node/services/UniquenessProvider.kt:13-35 as
+ *                                 InMemoryUniquenessProvider.kt:14-36 decides it (the decision half of
+ *                                 PersistentUniquenessProvider.kt:61-81), for NotaryFlow.kt:133-141: a device-resident
+ *                                 set of consumed states, a batch decided exactly as sequential commits would
  *
  * Conventions
  *   - Return codes: CV_OK (0) or a negative CV_E* code; nothing throws, aborts or longjmps across
@@ -287,6 +292,80 @@ void cv_signer_close(cv_signer *s);
 int cv_ed25519_sign_keyed(cv_ctx *ctx, const cv_signer *s, size_t n, const uint8_t *msg_arena,
                           uint64_t msg_arena_bytes, const uint64_t *msg_off, const uint32_t *msg_len,
                           uint8_t *sig_out /* n*64 */);
+
+/* A uniqueness set: the notary's map of consumed states (InMemoryUniquenessProvider.committedStates,
+ * node/src/main/kotlin/net/corda/node/services/transactions/InMemoryUniquenessProvider.kt:14-36; the table of
+ * PersistentUniquenessProvider.kt:19-81), resident on ONE device of the context: `device` is an index into the
+ * context's devices (0 for a context of one).  It maps a 32-byte state key, all 32 bytes the identity, to the
+ * consuming record UniquenessProvider.ConsumingTx(id[32], inputIndex u32, requestingParty) (UniquenessProvider.kt:31);
+ * the party is a u32 handle, the binding keeps the Party table.  The binding chooses the key; the documented
+ * choice is SecureHash.sha256 of the serialised StateRef (Structures.kt:337), the input's Merkle leaf hash.
+ *   - Open addressing over a power-of-two slot count of at least 2 x capacity (16 at the least), about 76 bytes a
+ *     slot.  Slots are chosen by a hash of the whole key mixed with a per-set random seed, never by key bits: keys
+ *     are SHA-256 outputs a submitter can grind.  Nothing is deleted.
+ *   - A call that would take the set past its capacity (resident + the call's states, repeats included) returns
+ *     CV_E_OOM before any change to the set and before any output is written; cv_uniq_reserve makes room (a rehash
+ *     on the device into a larger table; it never shrinks).
+ *   - Calls on one set serialise on a mutex in the set (the reference's ThreadBox); all are synchronous.  The set
+ *     has a stream and a workspace of its own, so it runs beside the context's other calls.  It is not durable: a
+ *     restarted notary warms it with cv_uniq_load from its commit log.
+ *   - More than 0xfffffffe requests, states or keys: CV_E_TOO_LARGE; so is a capacity, or one call, of more than
+ *     2^30 states.  A count of 0 returns CV_OK and touches nothing.  cv_uniq_close(NULL) is a no-op; a set is
+ *     closed before its context. */
+typedef struct cv_uniq cv_uniq;
+#define CV_UNIQ_OK 0
+#define CV_UNIQ_CONFLICT 1
+#define CV_UNIQ_SKIPPED 2
+int cv_uniq_open(cv_ctx *ctx, int device, size_t capacity_states, cv_uniq **out);
+void cv_uniq_close(cv_uniq *u);
+int cv_uniq_reserve(cv_uniq *u, size_t capacity_states);
+
+/* N x UniquenessProvider.commit(states, txId, callerIdentity) (UniquenessProvider.kt:13-35; NotaryFlow.kt:133-141
+ * commitInputStates), decided EXACTLY as ntx sequential commit calls in request order (InMemoryUniquenessProvider.kt:
+ * 20-35).  Request t holds states [tx_state_begin[t], tx_state_begin[t+1]) (begin[0] == 0, monotone: CV_E_ARGS
+ * otherwise), its id is tx_id[t], its caller caller[t].
+ *   - tx_enable[t] == 0 (NULL: all enabled): the request is skipped; it commits nothing, conflicts with nothing,
+ *     tx_status[t] = CV_UNIQ_SKIPPED.
+ *   - A request conflicts iff one of its states is in the set when its turn comes: resident before the call, or
+ *     put by an EARLIER ACCEPTED request of this batch.  It commits nothing; tx_status[t] = CV_UNIQ_CONFLICT,
+ *     state_conflict[i] = 1 and consumed_id / consumed_index / consumed_caller[i] = the consuming record for each
+ *     conflicting state i, state_conflict[i] = 0 and a zero record for its other states.
+ *   - Otherwise tx_status[t] = CV_UNIQ_OK and every state is put with (tx_id[t], its index in the request,
+ *     caller[t]); a state the request repeats is re-put, so the last index wins.  A request without states is
+ *     accepted.  state_conflict and the records of skipped and accepted requests are zero. */
+int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key /* nstates*32 */,
+                         const uint32_t *tx_state_begin /* ntx+1 */, const uint8_t *tx_id /* ntx*32 */,
+                         const uint32_t *caller /* ntx */, const uint8_t *tx_enable /* ntx, NULL = all */,
+                         uint8_t *tx_status /* ntx */, uint8_t *state_conflict /* nstates */,
+                         uint8_t *consumed_id /* nstates*32 */, uint32_t *consumed_index /* nstates */,
+                         uint32_t *consumed_caller /* nstates */);
+
+/* committedStates[key] for n keys (InMemoryUniquenessProvider.kt:24; PersistentUniquenessProvider.kt:66): found[i]
+ * = 1 and the consuming record, or 0 and a zero record.  Read-only. */
+int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key /* n*32 */, uint8_t *found /* n */,
+                   uint8_t *consumed_id /* n*32 */, uint32_t *consumed_index /* n */, uint32_t *consumed_caller /* n */);
+
+/* Warms the set from a durable log (the rows of PersistentUniquenessProvider's node_notary_commit_log,
+ * PersistentUniquenessProvider.kt:30-49).  The keys must be distinct within the call and not resident:
+ * otherwise CV_E_ARGS, the set unchanged (the check runs on the device before the first insert). */
+int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key /* n*32 */, const uint8_t *consumed_id /* n*32 */,
+                 const uint32_t *consumed_index /* n */, const uint32_t *consumed_caller /* n */);
+
+/* The parallel decision rounds a commit runs at the most before one lane decides the requests still open in order
+ * (0 = that serial tail only; at the most 64; default 8).  A batch without conflicts needs one round, a chain of k
+ * requests each conflicting with the one before it k.  The result never depends on it: tests force each path. */
+int cv_uniq_set_max_rounds(cv_uniq *u, int rounds);
+
+/* Diagnostics: out[k] for k < nout (CV_UNIQ_STAT_*; entries past CV_UNIQ_STAT_COUNT are zero). */
+#define CV_UNIQ_STAT_RESIDENT 0   /* states in the set */
+#define CV_UNIQ_STAT_CAPACITY 1
+#define CV_UNIQ_STAT_SLOTS 2
+#define CV_UNIQ_STAT_ROUNDS 3     /* rounds the last commit ran */
+#define CV_UNIQ_STAT_TAIL 4       /* requests the last commit's serial tail decided */
+#define CV_UNIQ_STAT_PROBE 5      /* longest probe of the table in the last call, in slots */
+#define CV_UNIQ_STAT_WRAPS 6      /* probes that passed the table's last slot, since open */
+#define CV_UNIQ_STAT_COUNT 7
+int cv_uniq_stats(cv_uniq *u, uint64_t *out, size_t nout);
 
 /* tx_ok[t] = AND of verdict bits [tx_sig_begin[t], tx_sig_begin[t+1]); a transaction with no
  * signatures is not ok (SignedTransaction requires sigs.isNotEmpty(), SignedTransaction.kt:27-29). */
