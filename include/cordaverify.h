@@ -58,6 +58,16 @@
  *     bytes are not a valid point: the reference throws IllegalArgumentException when building the
  *     EdDSAPublicKey).  Length errors (sig != 64 B -> SignatureException, key != 32 B) cannot be
  *     expressed in these fixed-width records; the host shim rejects them before the call.
+ *   - Outputs, both APIs (tests/test_gpu_output_contract.py, tests/test_gpu_host_output_contract.py):
+ *       prior contents  Outputs may hold anything on entry: a successful call writes every byte of every output
+ *                       it is given (of the node arrays: the *nnodes entries used) and nothing before or behind
+ *                       it; it never ORs into, or relies on, what was there.  Inputs are only read.
+ *       tail bits       The bits of the last bitmap word at and above n are written as zero.
+ *       empty tx        The id of a transaction without leaves (CV_TX_EMPTY) is 32 zero bytes.
+ *       nothing to do   A count of 0 returns CV_OK and writes no output byte; neither does the CV_E_ARGS return of
+ *                       a bounded call without a ticket whose records reach past the arena, nor CV_E_OOM of the
+ *                       uniqueness set.
+ *     Host arrays need the alignment of their C type and no more (the device-resident API: see its section).
  *   - Multi-GPU: cv_open(mask) with several bits set routes host-buffer batches over the devices: a batch
  *     up to CV_OPT_SHARD_MIN records goes whole to the least loaded device; a throughput batch (from
  *     CV_OPT_SPREAD_MIN records) is cut into contiguous ranges (multiples of 64) over all of them; a batch
@@ -410,6 +420,15 @@ int cv_verify_transactions_ex(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena
  * Calls may use different streams, from any thread: the engine orders every use of a device's shared
  * verify workspace and key pool (a call on a new stream first waits for the previous call's work on
  * that workspace), so concurrent calls serialise on the device instead of racing.
+ * Alignment (the kernels' vector accesses need it; a pointer below it faults the GPU, nothing checks it):
+ *     16 bytes  d_pk, d_sig, d_keys, d_seed (inputs and outputs: records are read and written as 16-byte vectors),
+ *               d_ids, d_workspace
+ *      8 bytes  d_bitmap (whole 64-bit words, 64-bit atomics), d_off, d_leaf_off
+ *      4 bytes  d_len, d_leaf_len, d_key_index, d_tx_leaf_begin
+ *      none     d_status, d_tx_status, d_arena (messages and leaves may start at any byte; the engine reads the
+ *               aligned 32-bit words that hold their bytes, never a word that holds none)
+ * Outputs as under Conventions: any prior contents, zero tail bits in d_bitmap, ceil(n/64) * 8 bytes of it written
+ * and not one more, a zero id for an empty transaction; n == 0 (ntx == 0) enqueues nothing.
  */
 int cv_ed25519_verify_device(cv_ctx *ctx, int device, size_t n, const void *d_pk, const void *d_sig,
                              const void *d_arena, const void *d_off, const void *d_len, void *d_bitmap,
