@@ -24,9 +24,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 # kernel translation units (cv_kcommon.h) compile in parallel; cv_kernels.hip holds the launchers
 SOURCES = ["cv_k_hs.hip", "cv_k_hss.hip", "cv_k_lat.hip", "cv_k_keyed.hip", "cv_k_misc.hip", "cv_k_sign.hip",
-           "cv_k_pmt.hip", "cv_k_uniq.hip", "cv_kernels.hip", "cv_api.cpp"]
+           "cv_k_pmt.hip", "cv_k_uniq.hip", "cv_kernels.hip", "cv_api.cpp", "cv_api_sign.cpp", "cv_api_pmt.cpp",
+           "cv_api_uniq.cpp"]
 # host symbols hidden: the library exports only the cv_* entry points include/cordaverify.h declares
-# (cv_api.cpp gives the header's declarations default visibility); the cvk_* launchers stay internal
+# (cv_host.h gives the header's declarations default visibility); the cvk_* launchers stay internal
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Xarch_host", "-fvisibility=hidden"]
 # kernels: LLVM's max-ILP machine scheduler (A/B on one MI355X, 3 alternating rounds: C2 1M verify
@@ -81,8 +82,10 @@ def build(verbose: bool = False, force: bool = False) -> str:
             if verbose and r.stderr.strip():
                 sys.stderr.write(r.stderr)
     if force or _stale(LIB, objs):
-        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs + ["-lpthread",
-                                                                                 f"-Wl,--version-script={MAPFILE}"]
+        # --no-undefined: a launcher (or kernel stub) missing from the objects is a link error, not a symbol left
+        # for the loader to miss at its first call
+        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs + [
+            "-lpthread", "-Wl,--no-undefined", f"-Wl,--version-script={MAPFILE}"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)

@@ -1,0 +1,350 @@
+// cv_api_uniq.cpp — the device-resident uniqueness set of the C-ABI (include/cordaverify.h): struct cv_uniq and
+// the cv_uniq_* entry points.  The engine state is cv_host.h's.
+#include "cv_host.h"
+
+using namespace cvh;
+
+extern "C" {
+
+// ---------------------------------------------------------------- uniqueness set (the notary's commit step)
+// The set lives on one device of its context, with a stream, a workspace and a pinned read-back block of its own,
+// so its calls take no device lock: they serialise on the set's mutex (the reference's ThreadBox).  The table is
+// five arrays in ONE allocation (occ | key | id | index | caller, cv_uniq.h); growth builds a second one, rehashes on
+// the device and frees the first.
+struct cv_uniq {
+    cv_ctx *ctx = nullptr;
+    int ordinal = 0;
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    void *tab = nullptr;
+    CvUniqTable T{};
+    size_t capacity = 0, resident = 0;
+    DevBuf ws, dstat;
+    uint32_t *hstat = nullptr;               // pinned: the device counters read back
+    int max_rounds = 8;
+    uint64_t last_rounds = 0, last_tail = 0, last_probe = 0, wraps = 0;
+};
+
+static const size_t kUniqMaxStates = (size_t)1 << 30;   // a table's slot count stays within 2^31
+
+static size_t uniq_slots(size_t capacity) {
+    size_t s = 16;
+    while (s < 2 * capacity) s <<= 1;
+    return s;
+}
+
+static void uniq_carve(void *base, size_t slots, uint64_t seed, CvUniqTable *T) {
+    uint32_t *p = static_cast<uint32_t *>(base);
+    T->occ = p;
+    T->key = p + slots;
+    T->id = p + 9 * slots;
+    T->index = p + 17 * slots;
+    T->caller = p + 18 * slots;
+    T->mask = (uint32_t)(slots - 1);
+    T->seed = seed;
+}
+
+// a fresh, empty table for `capacity` states on the current device
+static int uniq_alloc(size_t capacity, uint64_t seed, hipStream_t s, void **base, CvUniqTable *T) {
+    const size_t slots = uniq_slots(capacity);
+    void *p = nullptr;
+    CV_TRY(hipMalloc(&p, 76 * slots));
+    const hipError_t e = hipMemsetAsync(p, 0, 4 * slots, s);     // occ; the other arrays are written before they are read
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_rc(e);
+    }
+    *base = p;
+    uniq_carve(p, slots, seed, T);
+    return CV_OK;
+}
+
+// counters zeroed before a call's kernels / read back and folded into the set's statistics after them
+static int uniq_stat_begin(cv_uniq *u) {
+    CV_TRY(hipMemsetAsync(u->dstat.p, 0, 4 * CVU_D_WORDS, u->stream));
+    return CV_OK;
+}
+static int uniq_stat_read(cv_uniq *u) {
+    CV_TRY(hipMemcpyAsync(u->hstat, u->dstat.p, 4 * CVU_D_WORDS, hipMemcpyDeviceToHost, u->stream));
+    CV_TRY(hipStreamSynchronize(u->stream));
+    return CV_OK;
+}
+static int uniq_stat_end(cv_uniq *u) {
+    const int rc = uniq_stat_read(u);
+    if (rc != CV_OK) return rc;
+    u->last_probe = u->hstat[CVU_D_MAXPROBE];
+    u->wraps += u->hstat[CVU_D_WRAPS];
+    return u->hstat[CVU_D_ERROR] ? CV_E_HIP : CV_OK;            // a probe ran out of slots: never with the sizes above
+}
+
+int cv_uniq_open(cv_ctx *ctx, int device, size_t capacity_states, cv_uniq **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || device < 0 || (size_t)device >= ctx->devs.size()) return CV_E_ARGS;
+    if (capacity_states > kUniqMaxStates) return CV_E_TOO_LARGE;
+    std::unique_ptr<cv_uniq> u(new (std::nothrow) cv_uniq());
+    if (!u) return CV_E_OOM;
+    u->ctx = ctx;
+    u->ordinal = ctx->devs[(size_t)device]->ordinal;
+    u->capacity = std::max<size_t>(capacity_states, 1);
+    std::random_device rd;
+    const uint64_t seed = key_seed(0) ^ (((uint64_t)rd() << 32) | rd());
+    int rc = hip_rc(hipSetDevice(u->ordinal));
+    if (rc == CV_OK) rc = hip_rc(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
+    if (rc == CV_OK) rc = hip_rc(hipHostMalloc(reinterpret_cast<void **>(&u->hstat), 4 * CVU_D_WORDS, hipHostMallocDefault));
+    if (rc == CV_OK) rc = hip_rc(u->dstat.ensure(4 * CVU_D_WORDS, false));
+    if (rc == CV_OK) rc = uniq_alloc(u->capacity, seed, u->stream, &u->tab, &u->T);
+    if (rc == CV_OK) rc = hip_rc(hipStreamSynchronize(u->stream));
+    if (rc != CV_OK) {
+        cv_uniq_close(u.release());
+        return rc;
+    }
+    *out = u.release();
+    return CV_OK;
+}
+
+void cv_uniq_close(cv_uniq *u) {
+    if (!u) return;
+    (void)hipSetDevice(u->ordinal);
+    if (u->stream) (void)hipStreamSynchronize(u->stream);
+    if (u->tab) (void)hipFree(u->tab);
+    u->ws.release();
+    u->dstat.release();
+    if (u->hstat) (void)hipHostFree(u->hstat);
+    if (u->stream) (void)hipStreamDestroy(u->stream);
+    delete u;
+}
+
+int cv_uniq_reserve(cv_uniq *u, size_t capacity_states) {
+    if (!u) return CV_E_ARGS;
+    if (capacity_states > kUniqMaxStates) return CV_E_TOO_LARGE;
+    std::lock_guard<std::mutex> g(u->mu);
+    if (capacity_states <= u->capacity) return CV_OK;            // never shrinks
+    CV_TRY(hipSetDevice(u->ordinal));
+    if (uniq_slots(capacity_states) == (size_t)u->T.mask + 1) {  // the slots already hold it
+        u->capacity = capacity_states;
+        return CV_OK;
+    }
+    void *base = nullptr;
+    CvUniqTable to{};
+    int rc = uniq_alloc(capacity_states, u->T.seed, u->stream, &base, &to);
+    if (rc != CV_OK) return rc;
+    rc = uniq_stat_begin(u);
+    if (rc == CV_OK) rc = hip_rc(cvk_uniq_rehash(&u->T, &to, u->dstat.as<uint32_t>(), u->stream));
+    const int rc2 = uniq_stat_end(u);                            // synchronises, also after a failed launch
+    if (rc == CV_OK) rc = rc2;
+    if (rc != CV_OK) {
+        (void)hipFree(base);                                     // the old table is untouched
+        return rc;
+    }
+    (void)hipFree(u->tab);
+    u->tab = base;
+    u->T = to;
+    u->capacity = capacity_states;
+    return CV_OK;
+}
+
+int cv_uniq_set_max_rounds(cv_uniq *u, int rounds) {
+    if (!u || rounds < 0 || rounds > CVU_MAX_ROUNDS) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    u->max_rounds = rounds;
+    return CV_OK;
+}
+
+int cv_uniq_stats(cv_uniq *u, uint64_t *out, size_t nout) {
+    if (!u || (nout && !out)) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    const uint64_t v[CV_UNIQ_STAT_COUNT] = {u->resident, u->capacity, (uint64_t)u->T.mask + 1, u->last_rounds,
+                                            u->last_tail, u->last_probe, u->wraps};
+    for (size_t k = 0; k < nout; k++) out[k] = k < CV_UNIQ_STAT_COUNT ? v[k] : 0;
+    return CV_OK;
+}
+
+// begin[0] == 0 and monotone
+static bool uniq_ranges_ok(size_t ntx, const uint32_t *begin) {
+    if (begin[0] != 0) return false;
+    for (size_t t = 0; t < ntx; t++)
+        if (begin[t + 1] < begin[t]) return false;
+    return true;
+}
+
+static uint32_t uniq_bmask(size_t nstates) {
+    size_t s = 16;
+    while (s < 2 * nstates) s <<= 1;
+    return (uint32_t)(s - 1);
+}
+
+int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const uint32_t *tx_state_begin,
+                         const uint8_t *tx_id, const uint32_t *caller, const uint8_t *tx_enable, uint8_t *tx_status,
+                         uint8_t *state_conflict, uint8_t *consumed_id, uint32_t *consumed_index,
+                         uint32_t *consumed_caller) {
+    if (ntx == 0) return CV_OK;
+    if (ntx > 0xfffffffeull) return CV_E_TOO_LARGE;
+    if (!tx_state_begin || !tx_id || !caller || !tx_status) return CV_E_ARGS;
+    if (!uniq_ranges_ok(ntx, tx_state_begin)) return CV_E_ARGS;
+    const size_t S = tx_state_begin[ntx];
+    if (S > 0xfffffffeull) return CV_E_TOO_LARGE;
+    if (S && (!state_key || !state_conflict || !consumed_id || !consumed_index || !consumed_caller)) return CV_E_ARGS;
+    if (ntx > kUniqMaxStates || S > kUniqMaxStates) return CV_E_TOO_LARGE;
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    if (u->resident + S > u->capacity) return CV_E_OOM;          // before any change and any output
+    CV_TRY(hipSetDevice(u->ordinal));
+    const size_t T = ntx, bs = (size_t)uniq_bmask(S) + 1;
+    // inputs | workspace | outputs (tx_status | state_conflict | consumed id, index, caller: one copy-back region)
+    const size_t o_key = 0, o_beg = o_key + al16(32 * S), o_id = o_beg + al16(4 * (T + 1)), o_cal = o_id + al16(32 * T);
+    const size_t o_en = o_cal + al16(4 * T), o_bt = o_en + al16(T), o_rep = o_bt + al16(4 * bs), o_res = o_rep + al16(4 * S);
+    const size_t o_stx = o_res + al16(4 * S), o_own = o_stx + al16(4 * S), o_last = o_own + al16(4 * S);
+    const size_t o_s0 = o_last + al16(4 * S), o_s1 = o_s0 + al16(4 * T), o_ts = o_s1 + al16(4 * T);
+    const size_t o_sc = o_ts + al16(T), o_cid = o_sc + al16(S), o_cix = o_cid + al16(32 * S), o_cc = o_cix + al16(4 * S);
+    const size_t total = o_cc + al16(4 * S) + 16;
+    CV_TRY(u->ws.ensure(total));
+    uint8_t *base = u->ws.as<uint8_t>();
+    auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
+    hipStream_t s = u->stream;
+    auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });   // the pageable copies read the caller's arrays
+    if (S) CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * S, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemcpyAsync(base + o_beg, tx_state_begin, 4 * (T + 1), hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemcpyAsync(base + o_id, tx_id, 32 * T, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemcpyAsync(base + o_cal, caller, 4 * T, hipMemcpyHostToDevice, s));
+    if (tx_enable) CV_TRY(hipMemcpyAsync(base + o_en, tx_enable, T, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemsetAsync(base + o_cid, 0, o_cc + al16(4 * S) - o_cid, s));   // records of states without a conflict: zero
+    int rc = uniq_stat_begin(u);
+    if (rc != CV_OK) return rc;
+    CvUniqBatch B{};
+    B.ntx = (uint32_t)T;
+    B.nstates = (uint32_t)S;
+    B.key = u32(o_key);
+    B.begin = u32(o_beg);
+    B.id = u32(o_id);
+    B.caller = u32(o_cal);
+    B.enable = tx_enable ? base + o_en : nullptr;
+    B.btab = u32(o_bt);
+    B.bmask = (uint32_t)(bs - 1);
+    B.rep = u32(o_rep);
+    B.res = u32(o_res);
+    B.state_tx = u32(o_stx);
+    B.owner = u32(o_own);
+    B.last = u32(o_last);
+    B.tx_status = base + o_ts;
+    B.state_conflict = base + o_sc;
+    B.cons_id = u32(o_cid);
+    B.cons_index = u32(o_cix);
+    B.cons_caller = u32(o_cc);
+    B.dstat = u->dstat.as<uint32_t>();
+    uint32_t *cur = u32(o_s0), *nxt = u32(o_s1);
+    CV_TRY(cvk_uniq_front(&u->T, &B, cur, s));
+    // rounds while the device says a request is undecided (one 4-byte read-back per round), then the serial tail
+    // for what max_rounds left; with no round run the count is unknown and the tail looks for itself
+    uint64_t rounds = 0;
+    bool undecided = true;
+    while (undecided && rounds < (uint64_t)u->max_rounds) {
+        CV_TRY(cvk_uniq_round(&B, cur, nxt, (uint32_t)rounds, s));
+        std::swap(cur, nxt);
+        CV_TRY(hipMemcpyAsync(u->hstat, B.dstat + CVU_D_ROUND0 + rounds, 4, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipStreamSynchronize(s));
+        undecided = u->hstat[0] != 0;
+        rounds++;
+    }
+    CV_TRY(cvk_uniq_finish(&u->T, &B, cur, undecided ? 1 : 0, s));
+    CV_TRY(hipMemcpyAsync(tx_status, base + o_ts, T, hipMemcpyDeviceToHost, s));
+    if (S) {
+        CV_TRY(hipMemcpyAsync(state_conflict, base + o_sc, S, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipMemcpyAsync(consumed_id, base + o_cid, 32 * S, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipMemcpyAsync(consumed_index, base + o_cix, 4 * S, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipMemcpyAsync(consumed_caller, base + o_cc, 4 * S, hipMemcpyDeviceToHost, s));
+    }
+    rc = uniq_stat_end(u);
+    drain.armed = false;
+    u->resident += u->hstat[CVU_D_INSERTED];
+    u->last_rounds = rounds;
+    u->last_tail = u->hstat[CVU_D_TAIL];
+    return rc;
+}
+
+int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key, uint8_t *found, uint8_t *consumed_id,
+                   uint32_t *consumed_index, uint32_t *consumed_caller) {
+    if (n == 0) return CV_OK;
+    if (n > 0xfffffffeull) return CV_E_TOO_LARGE;
+    if (!state_key || !found || !consumed_id || !consumed_index || !consumed_caller) return CV_E_ARGS;
+    if (n > kUniqMaxStates) return CV_E_TOO_LARGE;
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    CV_TRY(hipSetDevice(u->ordinal));
+    const size_t o_key = 0, o_f = o_key + al16(32 * n), o_cid = o_f + al16(n), o_cix = o_cid + al16(32 * n);
+    const size_t o_cc = o_cix + al16(4 * n), total = o_cc + al16(4 * n) + 16;
+    CV_TRY(u->ws.ensure(total));
+    uint8_t *base = u->ws.as<uint8_t>();
+    auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
+    hipStream_t s = u->stream;
+    auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
+    CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * n, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemsetAsync(base + o_cid, 0, total - 16 - o_cid, s));            // absent keys: zero records
+    int rc = uniq_stat_begin(u);
+    if (rc != CV_OK) return rc;
+    CV_TRY(cvk_uniq_lookup(&u->T, (uint32_t)n, u32(o_key), base + o_f, u32(o_cid), u32(o_cix), u32(o_cc),
+                           u->dstat.as<uint32_t>(), s));
+    CV_TRY(hipMemcpyAsync(found, base + o_f, n, hipMemcpyDeviceToHost, s));
+    CV_TRY(hipMemcpyAsync(consumed_id, base + o_cid, 32 * n, hipMemcpyDeviceToHost, s));
+    CV_TRY(hipMemcpyAsync(consumed_index, base + o_cix, 4 * n, hipMemcpyDeviceToHost, s));
+    CV_TRY(hipMemcpyAsync(consumed_caller, base + o_cc, 4 * n, hipMemcpyDeviceToHost, s));
+    rc = uniq_stat_end(u);
+    drain.armed = false;
+    return rc;
+}
+
+int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *consumed_id,
+                 const uint32_t *consumed_index, const uint32_t *consumed_caller) {
+    if (n == 0) return CV_OK;
+    if (n > 0xfffffffeull) return CV_E_TOO_LARGE;
+    if (!state_key || !consumed_id || !consumed_index || !consumed_caller) return CV_E_ARGS;
+    if (n > kUniqMaxStates) return CV_E_TOO_LARGE;
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    if (u->resident + n > u->capacity) return CV_E_OOM;
+    CV_TRY(hipSetDevice(u->ordinal));
+    const size_t bs = (size_t)uniq_bmask(n) + 1;
+    const size_t o_key = 0, o_id = o_key + al16(32 * n), o_ix = o_id + al16(32 * n), o_cal = o_ix + al16(4 * n);
+    const size_t o_bt = o_cal + al16(4 * n), o_rep = o_bt + al16(4 * bs), o_res = o_rep + al16(4 * n);
+    const size_t total = o_res + al16(4 * n) + 16;
+    CV_TRY(u->ws.ensure(total));
+    uint8_t *base = u->ws.as<uint8_t>();
+    auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
+    hipStream_t s = u->stream;
+    auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
+    CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * n, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemcpyAsync(base + o_id, consumed_id, 32 * n, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemcpyAsync(base + o_ix, consumed_index, 4 * n, hipMemcpyHostToDevice, s));
+    CV_TRY(hipMemcpyAsync(base + o_cal, consumed_caller, 4 * n, hipMemcpyHostToDevice, s));
+    int rc = uniq_stat_begin(u);
+    if (rc != CV_OK) return rc;
+    CvUniqBatch B{};
+    B.nstates = (uint32_t)n;
+    B.key = u32(o_key);
+    B.id = u32(o_id);
+    B.cons_index = u32(o_ix);
+    B.caller = u32(o_cal);
+    B.btab = u32(o_bt);
+    B.bmask = (uint32_t)(bs - 1);
+    B.rep = u32(o_rep);
+    B.res = u32(o_res);
+    B.dstat = u->dstat.as<uint32_t>();
+    // the check first (a key repeated in the call, or resident): the set changes only after it passed
+    CV_TRY(cvk_uniq_load(&u->T, &B, 0, s));
+    rc = uniq_stat_read(u);
+    if (rc != CV_OK) return rc;
+    if (u->hstat[CVU_D_ERROR]) {
+        drain.armed = false;
+        return CV_E_HIP;
+    }
+    if (u->hstat[CVU_D_BAD]) {
+        drain.armed = false;
+        return CV_E_ARGS;
+    }
+    CV_TRY(cvk_uniq_load(&u->T, &B, 1, s));
+    rc = uniq_stat_end(u);
+    drain.armed = false;
+    if (rc == CV_OK) u->resident += n;
+    return rc;
+}
+
+}  // extern "C"

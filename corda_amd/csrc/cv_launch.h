@@ -1,5 +1,5 @@
-// cv_launch.h — internal ABI between the host library (cv_api.cpp) and the kernel launchers
-// (cv_kernels.hip).  Not part of the public C-ABI (include/cordaverify.h).
+// cv_launch.h — internal ABI between the host library (cv_api.cpp and the cv_api_*.cpp feature units, through
+// cv_host.h) and the kernel launchers (cv_kernels.hip).  Not part of the public C-ABI (include/cordaverify.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,7 +7,7 @@
 #include "cv_uniq.h"
 
 // Helper stream and events of one verify workspace slot, used by cvk_verify's drain overlap (a
-// near-empty last round of a chunk is filled by a tail sub-chunk on s2).  Owned by cv_api.cpp (one per
+// near-empty last round of a chunk is filled by a tail sub-chunk on s2).  Owned by cv_host.h's Slot (one per
 // workspace slot, so two slots' calls never share a helper stream); cvk_verify only records and waits.
 struct CvkSplit {
     hipStream_t s2 = nullptr;

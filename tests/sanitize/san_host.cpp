@@ -1,11 +1,15 @@
 // san_host.cpp — TEST INFRASTRUCTURE: the host-only logic of the C-ABI library (corda_amd/csrc/cv_api.cpp)
 // built with AddressSanitizer + UndefinedBehaviorSanitizer (or ThreadSanitizer) and exercised without a
-// GPU.  cv_api.cpp is included whole so its file-local functions are reachable; the kernel launchers it
-// calls (cv_launch.h) are stubs that never run.  Checked here:
+// GPU.  cv_api.cpp — the core of the library: contexts, routing, the host pipeline, tickets; with cv_host.h (the
+// engine state) and cv_stage.h (staging, dedupe, sub-chunk plans) — is included whole so its file-local functions
+// are reachable; the kernel launchers it calls (cv_launch.h) are stubs that never run.  The signer, the partial
+// Merkle trees and the uniqueness set are translation units of their own (cv_api_sign.cpp, cv_api_pmt.cpp,
+// cv_api_uniq.cpp) and are not part of this program.  Checked here:
 //   dedupe_keys          key dedupe of cv_ed25519_verify_batch (pools, gate, slices on a pool, first-seen order)
 //   WorkerPool/par_copy  the packing thread pool and its pinned-staging copies (piece boundaries, empty jobs)
 //   stage_plan/_pack     staging layout of a record range (arena range and compact gather forms)
 //   pipe_cuts            the host pipeline's sub-chunk plan (64-aligned, covering, balanced tail)
+//   merkle_cuts          the Merkle sub-chunk plan (whole transactions, leaf targets, ramp, 32-bit clamp)
 //   dispatch             routing: shard ranges over k devices, per-device exclusion, concurrent callers
 //   mstage_plan/_pack    Merkle staging of a transaction range (non-monotone offsets, empty txs, compact)
 //   cv_tx_verdicts       per-transaction AND
@@ -20,11 +24,6 @@ extern "C" {
 hipError_t cvk_verify(const CvkPlan *, uint32_t, const uint8_t *, const uint8_t *, const uint8_t *, const uint64_t *,
                       const uint32_t *, uint64_t *, uint8_t *, uint32_t *, uint8_t *, uint32_t *, uint32_t, hipStream_t,
                       hipEvent_t *, const CvkSplit *, const CvkPrepOverlap *) { return hipErrorNoDevice; }
-hipError_t cvk_sign(uint32_t, const uint8_t *, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *, uint8_t *,
-                    hipStream_t) { return hipErrorNoDevice; }
-hipError_t cvk_pmt_verify(uint32_t, const uint8_t *, const uint32_t *, const uint32_t *, const uint8_t *, const uint32_t *,
-                          const uint8_t *, const uint8_t *, const uint32_t *, uint32_t *, uint8_t *, uint8_t *, uint8_t *,
-                          hipStream_t) { return hipErrorNoDevice; }
 hipError_t cvk_merkle(uint32_t, uint32_t, uint32_t, const uint8_t *, const uint64_t *, const uint32_t *, const uint32_t *,
                       uint32_t *, uint8_t *, uint8_t *, hipStream_t) { return hipErrorNoDevice; }
 hipError_t cvk_tx_sig_refs(uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, uint64_t *, uint32_t *, hipStream_t) {
@@ -223,6 +222,49 @@ static void test_pipe_cuts() {
             }
         }
     }
+}
+
+// The Merkle sub-chunk plan, against its contract: the cuts run from t0 to t1 and strictly increase (whole
+// transactions, at least one each); sub-chunk k's target is `per` leaves, or with ramp max(1, per / 4) doubling up
+// to `per`; a sub-chunk holds more leaves than its target only when it is a single transaction, and ends before
+// t1 only where one more transaction would pass the target.  txb: 1 to 400 transactions of 0 to 9 leaves, empty
+// ones at both ends; then leaf indices just below 2^32, where the target is clamped to the last 32-bit index.
+static void check_merkle_cuts(const std::vector<uint32_t> &txb, size_t t0, size_t t1, size_t per, bool ramp) {
+    const std::vector<size_t> cut = merkle_cuts(txb.data(), t0, t1, per, ramp);
+    CHECK(cut.size() >= 2 && cut.front() == t0 && cut.back() == t1);
+    if (cut.size() < 2 || cut.front() != t0 || cut.back() != t1) return;
+    uint64_t target = ramp ? std::max<uint64_t>(1, per / 4) : per;
+    for (size_t j = 0; j + 1 < cut.size(); j++) {
+        const size_t a = cut[j], b = cut[j + 1];
+        CHECK(b > a && b <= t1);
+        if (b <= a || b > t1) return;
+        CHECK((uint64_t)txb[b] - txb[a] <= target || b == a + 1);
+        if (b < t1) CHECK((uint64_t)txb[b + 1] - txb[a] > target);
+        target = ramp ? std::min<uint64_t>(per, 2 * target) : per;
+    }
+}
+static void test_merkle_cuts() {
+    for (int rep = 0; rep < 200; rep++) {
+        const size_t ntx = rep < 4 ? (size_t)rep + 1 : rnd() % 400 + 1;
+        const size_t e0 = rnd() % 4, e1 = rnd() % 4;          // empty transactions at both ends
+        std::vector<uint32_t> txb(ntx + 1, 0);
+        for (size_t t = 0; t < ntx; t++)
+            txb[t + 1] = txb[t] + (uint32_t)(t < e0 || t + e1 >= ntx ? 0 : rnd() % 10);
+        for (size_t per : {1ul, 2ul, 3ul, 4ul, 7ul, 8ul, 9ul, 16ul, 33ul, 64ul})
+            for (bool ramp : {false, true}) {
+                check_merkle_cuts(txb, 0, ntx, per, ramp);
+                const size_t t0 = rnd() % ntx, t1 = t0 + 1 + rnd() % (ntx - t0);   // a shard inside the batch
+                check_merkle_cuts(txb, t0, t1, per, ramp);
+            }
+    }
+    // leaf indices just below 2^32: txb[c] + target passes the last 32-bit index and is clamped to it
+    std::vector<uint32_t> hi{0xFFFFFF00u};
+    for (int t = 0; t < 40; t++) hi.push_back(hi.back() + (uint32_t)(t % 7));
+    for (size_t per : {1ul, 5ul, 64ul, 200ul, 100000ul, (size_t)1 << 32})
+        for (bool ramp : {false, true}) check_merkle_cuts(hi, 0, hi.size() - 1, per, ramp);
+    hi.back() = UINT32_MAX;
+    check_merkle_cuts(hi, 0, hi.size() - 1, 64, true);
+    check_merkle_cuts(hi, 0, hi.size() - 1, 64, false);
 }
 
 // Merkle staging of transactions [t0, t1): leaf offsets not monotone (the arena holds the leaves in reverse
@@ -447,6 +489,7 @@ int main(int argc, char **argv) {
         test_mstage(false);
         test_mstage(true);
         test_pipe_cuts();
+        test_merkle_cuts();
         test_tx_verdicts();
         test_failed_finish_reaches_waiter();
         test_abi_guards();

@@ -2,7 +2,7 @@
 // __host__ __device__) on the CPU, for tests/test_uniq_cpu.py, which builds this file into tests/_build/libcvuniq.so,
 // and for tests/uniq_san.cpp, which includes it.
 //
-// A HSet is what cv_uniq is in cv_api.cpp, in host memory; huq_commit / huq_load / huq_lookup / huq_reserve run the
+// A HSet is what cv_uniq is in cv_api_uniq.cpp, in host memory; huq_commit / huq_load / huq_lookup / huq_reserve run the
 // steps the launchers of cv_kernels.hip enqueue (cvk_uniq_front, _round, _finish, _load, _lookup, _rehash), each
 // step's lanes ONE AFTER ANOTHER in the order `order` names: 0 ascending, 1 descending, 2 one fixed shuffle.  The
 // results must not depend on it.  Return codes as the C-ABI's: 0, -2 (a probe ran out), -3, -4.

@@ -14,7 +14,9 @@ pids=()
 for s in $D/corda_amd/csrc/*.hip; do
   /opt/rocm/bin/hipcc $F -mllvm -amdgpu-sched-strategy=max-ilp -c $s -o $D/obj/$(basename $s .hip).o & pids+=($!)
 done
-/opt/rocm/bin/hipcc -x hip $F -c $D/corda_amd/csrc/cv_api.cpp -o $D/obj/cv_api.o & pids+=($!)
+for s in $D/corda_amd/csrc/cv_api*.cpp; do
+  /opt/rocm/bin/hipcc -x hip $F -c $s -o $D/obj/$(basename $s .cpp).o & pids+=($!)
+done
 for p in "${pids[@]}"; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $D/libcv.so $D/obj/*.o -lpthread
 echo $D/libcv.so

@@ -1,13 +1,17 @@
-// gate_bench.cpp — host time of the key-dedupe gate (cv_api.cpp dedupe_gate), which every large
+// gate_bench.cpp — host time of the key-dedupe gate (cv_stage.h dedupe_gate), which every large
 // cv_ed25519_verify_batch call runs before its first DMA, on 1M / 8M distinct keys and on keys repeated 8 times
-// in a row, with the keys evicted from the caches before each call (a fresh call's state).  No GPU needed: the
-// engine's translation unit is included for its host code only and the kernel symbols are left unresolved.
-//   /opt/rocm/bin/hipcc -x hip --offload-host-only -O3 -std=c++17 -Iinclude -Icorda_amd/csrc \
-//       tools/microbench/gate_bench.cpp -o /tmp/gate_bench -lpthread -Wl,--unresolved-symbols=ignore-all
-#include "../../corda_amd/csrc/cv_api.cpp"
+// in a row, with the keys evicted from the caches before each call (a fresh call's state).  No GPU needed: only the
+// engine's staging header is included (host code, no devices or contexts), and the HIP runtime calls of its other
+// functions are left unresolved.
+//   /opt/rocm/bin/hipcc -x hip --offload-host-only -O3 -std=c++17 -Icorda_amd/csrc \
+//       tools/microbench/gate_bench.cpp -o tools/microbench/_bin/gate_bench -lpthread -Wl,--unresolved-symbols=ignore-all
+#include "../../corda_amd/csrc/cv_stage.h"
 
+#include <cstdio>
 #include <chrono>
 #include <random>
+
+using namespace cvh;
 
 int main() {
     static std::vector<uint8_t> junk(64 << 20);

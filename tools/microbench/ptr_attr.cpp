@@ -1,4 +1,4 @@
-// ptr_attr.cpp — host cost of hipPointerGetAttributes (the engine's pinned-input test, cv_api.cpp host_pinned) on
+// ptr_attr.cpp — host cost of hipPointerGetAttributes (the engine's pinned-input test, cv_stage.h host_pinned) on
 // pinned and pageable pointers, with few and with many live pinned allocations, and while another thread waits in
 // hipEventSynchronize on a long kernel (lock contention).
 //   hipcc -O2 ptr_attr.cpp -o ptr_attr && ./ptr_attr
