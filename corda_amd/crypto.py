@@ -268,7 +268,8 @@ class KeyPair:
 
 # ---------------------------------------------------------------- composite keys
 class CompositeKey:
-    """CompositeKey.kt:22-148: weighted-threshold key tree; fulfilment is pure host logic."""
+    """CompositeKey.kt:22-148: weighted-threshold key tree.  is_fulfilled_by is host logic, one tree at a time; a
+    batch's trees are decided on the device by cv_missing_signers (transactions.missing_signatures_batch)."""
 
     def is_fulfilled_by(self, keys) -> bool:
         raise NotImplementedError

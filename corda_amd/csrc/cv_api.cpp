@@ -248,7 +248,7 @@ void cv_close(cv_ctx *ctx) {
         (void)hipSetDevice(d.ordinal);
         (void)hipDeviceSynchronize();
         for (DevBuf *b : {&d.pk, &d.sig, &d.arena, &d.off, &d.len, &d.bitmap, &d.status, &d.seed, &d.tx_begin,
-                          &d.digest, &d.mdigest, &d.ids, &d.pmt, &d.kc.ktab, &d.kc.kok, &d.kc.keys, &d.kc.slots,
+                          &d.digest, &d.mdigest, &d.ids, &d.pmt, &d.ck, &d.kc.ktab, &d.kc.kok, &d.kc.keys, &d.kc.slots,
                           &d.kc.slot_of_key, &d.kc.scratch})
             b->release();
         d.pin_out.release();

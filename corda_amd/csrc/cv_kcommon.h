@@ -8,6 +8,7 @@
 //   cv_k_sign.hip  fixed-key signing (signer key expansion, one signature per lane)
 //   cv_k_pmt.hip   partial Merkle tree build (tear-offs): count, scan, emit
 //   cv_k_uniq.hip  the notary's uniqueness set (cv_uniq.h): group, rounds, tail, report + insert, load, lookup, rehash
+//   cv_k_ck.hip    missing signers (cv_ck.h): one lane per transaction, one wave per large transaction
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +17,7 @@
 #include "cv_quad.h"
 #include "cv_hsquad.h"
 #include "cv_uniq.h"
+#include "cv_ck.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -176,6 +178,9 @@ __global__ void cv_uniq_load_check_kernel(CvUniqBatch B);
 __global__ void cv_uniq_load_put_kernel(CvUniqTable T, CvUniqBatch B);
 __global__ void cv_uniq_lookup_kernel(CvUniqTable T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id, uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat);
 __global__ void cv_uniq_rehash_kernel(CvUniqTable from, CvUniqTable to, uint32_t *dstat);
+// missing signers (cv_k_ck.hip, cv_ck.h): the wide kernel's workgroups are one wave
+__global__ void cv_ck_narrow_kernel(CvCk C);
+__global__ void cv_ck_wide_kernel(CvCk C);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

@@ -406,6 +406,20 @@ hipError_t cvk_uniq_rehash(const CvUniqTable *from, const CvUniqTable *to, uint3
     return hipGetLastError();
 }
 
+// ---- missing signers (cv_ck.h): counter clear, one lane per transaction, one wave per listed transaction.  The wide
+// grid is fixed (the list's length stays on the device) and no larger than the batch: a transaction is listed once.
+hipError_t cvk_ck(const CvCk *a, hipStream_t stream) {
+    if (!a || a->ntx == 0 || !a->count || !a->list || !a->tx_status) return hipErrorInvalidValue;
+    CvCk C = *a;
+    if (C.wide_min == 0) C.wide_min = CV_CK_WIDE_DEFAULT;
+    hipError_t e = hipMemsetAsync(C.count, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cv_ck_narrow_kernel, dim3((C.ntx + CV_BLOCK - 1) / CV_BLOCK), dim3(CV_BLOCK), 0, stream, C);
+    if (C.wide_min != 0xffffffffu)
+        hipLaunchKernelGGL(cv_ck_wide_kernel, dim3(C.ntx < 1024u ? C.ntx : 1024u), dim3(64), 0, stream, C);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cv_ck.h"
 #include "cv_uniq.h"
 
 // Helper stream and events of one verify workspace slot, used by cvk_verify's drain overlap (a
@@ -93,6 +94,10 @@ hipError_t cvk_uniq_load(const CvUniqTable *T, const CvUniqBatch *B, int phase, 
 hipError_t cvk_uniq_lookup(const CvUniqTable *T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id,
                            uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat, hipStream_t stream);
 hipError_t cvk_uniq_rehash(const CvUniqTable *from, const CvUniqTable *to, uint32_t *dstat, hipStream_t stream);
+// Missing signers of a->ntx transactions (cv_ck.h; kernels in cv_k_ck.hip), enqueued on `stream`, nothing synchronised:
+// the list's counter cleared, the narrow kernel, then (unless wide_min is UINT32_MAX) the wide kernel over the list.
+// a->wide_min == 0 takes the default; count, list and flag point into the caller's workspace (cvck_ws_bytes).
+hipError_t cvk_ck(const CvCk *a, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

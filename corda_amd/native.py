@@ -28,6 +28,13 @@ CV_PMT_NOT_IN_TREE = 3
 CV_UNIQ_OK = 0
 CV_UNIQ_CONFLICT = 1
 CV_UNIQ_SKIPPED = 2
+CV_CK_LEAF = 0
+CV_CK_NODE = 1
+CV_VS_OK = 0
+CV_VS_BAD_SIGNATURE = 1
+CV_VS_MISSING = 2
+CV_VS_MALFORMED = 3
+CK_WIDE_DEFAULT, CK_WIDE_ALWAYS, CK_WIDE_NEVER = 0, 1, 0xFFFFFFFF      # cv_missing_signers' wide_min
 CV_UNIQ_STATS = ("resident", "capacity", "slots", "rounds", "tail", "probe", "wraps")   # CV_UNIQ_STAT_*
 
 # every symbol include/cordaverify.h declares (tests check the library exports all of them)
@@ -45,6 +52,7 @@ EXPORTED = (
     "cv_ed25519_sign_keyed_device", "cv_partial_merkle_build_bound", "cv_partial_merkle_build", "cv_filtered_build",
     "cv_uniq_open", "cv_uniq_close", "cv_uniq_reserve", "cv_uniq_commit_batch", "cv_uniq_lookup", "cv_uniq_load",
     "cv_uniq_set_max_rounds", "cv_uniq_stats",
+    "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -181,6 +189,12 @@ def load():
         lib.cv_uniq_set_max_rounds.restype = ctypes.c_int
         lib.cv_uniq_stats.argtypes = [_vp, _vp, _sz]
         lib.cv_uniq_stats.restype = ctypes.c_int
+        lib.cv_missing_signers.argtypes = [_vp] + [_sz] * 5 + [_vp] * 12 + [ctypes.c_uint32, _vp, _vp]
+        lib.cv_missing_signers.restype = ctypes.c_int
+        lib.cv_missing_signers_workspace.argtypes = [_sz, _sz]
+        lib.cv_missing_signers_workspace.restype = ctypes.c_uint64
+        lib.cv_missing_signers_device.argtypes = [_vp, ctypes.c_int] + [_sz] * 5 + [_vp] * 12 + [ctypes.c_uint32] + [_vp] * 4
+        lib.cv_missing_signers_device.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp]
         lib.cv_ed25519_sign_keyed.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed_device.argtypes = [_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -617,7 +631,66 @@ class Engine:
             self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
         return self._build_result(rc, "cv_filtered_build", ntx, cap, out, nn.value)
 
+    def missing_signers(self, kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key,
+                        tx_sig_begin, req_allowed=None, bitmap=None, wide_min: int = CK_WIDE_DEFAULT
+                        ) -> Tuple[np.ndarray, np.ndarray]:
+        """cv_missing_signers: the flat CompositeKey encoding of include/cordaverify.h (transactions.flatten_must_sign
+        builds it) -> (req_missing u8[nreq]: 0 fulfilled, 1 missing, 2 malformed; tx_status u8[ntx]: CV_VS_*).
+        req_allowed u8[nreq] and bitmap u64[ceil(nsig / 64)] are optional; wide_min forces a path (CK_WIDE_*)."""
+        def arr(a, dt, n, what, width=1):
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.size != n * width:
+                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
+            return a if a.size else np.zeros(width, dt)
+        tx_req_begin = np.ascontiguousarray(tx_req_begin, dtype=np.uint32)
+        tx_sig_begin = np.ascontiguousarray(tx_sig_begin, dtype=np.uint32)
+        req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32)
+        child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32)
+        ntx, nreq, nnodes = tx_req_begin.size - 1, req_begin.size - 1, child_begin.size - 1
+        if ntx < 0 or nreq < 0 or nnodes < 0 or tx_sig_begin.size != ntx + 1:
+            raise ValueError("the begin arrays must have count + 1 entries")
+        kind = arr(kind, np.uint8, nnodes, "kind")
+        leaf_key = arr(leaf_key, np.uint8, nnodes, "leaf_key", 32)
+        threshold = arr(threshold, np.int32, nnodes, "threshold")
+        child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
+        nchild = child.size
+        weight = arr(weight, np.int32, nchild, "weight")
+        if nchild == 0:
+            child = np.zeros(1, np.uint32)
+        sig_key = np.ascontiguousarray(sig_key, dtype=np.uint8).reshape(-1)
+        if sig_key.size % 32:
+            raise ValueError("sig_key must be rows of 32 bytes")
+        nsig = sig_key.size // 32
+        if nsig == 0:
+            sig_key = np.zeros(32, np.uint8)
+        if req_allowed is not None:
+            req_allowed = arr(req_allowed, np.uint8, nreq, "req_allowed")
+        if bitmap is not None:
+            bitmap = arr(bitmap, np.uint64, (nsig + 63) // 64, "bitmap")
+        req_missing = np.zeros(max(nreq, 1), np.uint8)
+        tx_status = np.zeros(max(ntx, 1), np.uint8)
+        _check(self._lib.cv_missing_signers(self._h, ntx, nreq, nnodes, nchild, nsig, _p(kind), _p(leaf_key), _p(threshold),
+                                            _p(child_begin), _p(child), _p(weight), _p(req_begin), _p(tx_req_begin),
+                                            _p(sig_key), _p(tx_sig_begin), _p(req_allowed), _p(bitmap),
+                                            ctypes.c_uint32(wide_min), _p(req_missing), _p(tx_status)),
+               "cv_missing_signers")
+        return req_missing[:nreq], tx_status[:ntx]
+
     # ------------------------------------------------------------ device-resident API
+    def missing_signers_device(self, device: int, ntx: int, nreq: int, nnodes: int, nchild: int, nsig: int, d_kind: int,
+                               d_leaf_key: int, d_threshold: int, d_child_begin: int, d_child: int, d_weight: int,
+                               d_req_begin: int, d_tx_req_begin: int, d_sig_key: int, d_tx_sig_begin: int,
+                               d_req_allowed: int, d_bitmap: int, wide_min: int, d_req_missing: int, d_tx_status: int,
+                               d_workspace: int, stream: int = 0):
+        """cv_missing_signers_device: enqueued on `stream`, nothing synchronised; d_workspace of
+        missing_signers_workspace(ntx, nnodes) bytes.  d_req_allowed / d_bitmap 0: none allowed / all valid."""
+        _check(self._lib.cv_missing_signers_device(
+            self._h, device, ntx, nreq, nnodes, nchild, nsig, d_kind or None, d_leaf_key or None, d_threshold or None,
+            d_child_begin or None, d_child or None, d_weight or None, d_req_begin or None, d_tx_req_begin or None,
+            d_sig_key or None, d_tx_sig_begin or None, d_req_allowed or None, d_bitmap or None,
+            ctypes.c_uint32(wide_min), d_req_missing or None, d_tx_status or None, d_workspace or None, stream or None),
+            "cv_missing_signers_device")
+
     def verify_device(self, device: int, n: int, d_pk: int, d_sig: int, d_arena: int, d_off: int, d_len: int,
                       d_bitmap: int, d_status: int = 0, stream: int = 0):
         _check(self._lib.cv_ed25519_verify_device(self._h, device, n, d_pk, d_sig, d_arena, d_off, d_len, d_bitmap,
@@ -875,6 +948,11 @@ def partial_merkle_build_bound(tx_leaf_begin) -> int:
     tx_leaf_begin = np.ascontiguousarray(tx_leaf_begin, dtype=np.uint32)
     ntx = tx_leaf_begin.shape[0] - 1
     return int(lib.cv_partial_merkle_build_bound(ntx, _p(tx_leaf_begin))) if ntx > 0 else 0
+
+
+def missing_signers_workspace(ntx: int, nnodes: int) -> int:
+    """cv_missing_signers_workspace: the bytes of missing_signers_device's d_workspace (host only)."""
+    return int(load().cv_missing_signers_workspace(ntx, nnodes))
 
 
 def bitmap_to_bools(bitmap: np.ndarray, n: int) -> np.ndarray:

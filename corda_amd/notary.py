@@ -40,7 +40,7 @@ from .crypto import (CompositeKey, DigitalSignature, EdDSAPublicKey, IllegalArgu
                      InvalidKeyException, KeyPair, SignatureException, VerifyItem, _prefilter, verify_many,
                      verify_with_ecdsa)
 from .transactions import (MerkleTreeException, SecureHash, SignaturesMissingException, SignedTransaction,
-                           WireTransaction, compute_ids)
+                           WireTransaction, compute_ids, missing_signatures_batch)
 
 
 # ---------------------------------------------------------------- timestamps (Structures.kt:412-423)
@@ -196,8 +196,11 @@ def verify_many_sharded(items: Sequence[VerifyItem], engine, group=None) -> List
 class BatchingNotary:
     def __init__(self, notary_seed: bytes, validating: bool = True, engine: Optional[native.Engine] = None,
                  uniqueness=None,
-                 timestamp_checker: Optional[TimestampChecker] = None, group=None):
+                 timestamp_checker: Optional[TimestampChecker] = None, group=None, device_signers: bool = False):
         self.engine = engine or native.default_engine()
+        # the missing signers of a whole batch in one device call (transactions.missing_signatures_batch) instead of
+        # one host evaluation per request; off by default, as the device uniqueness provider is
+        self.device_signers = device_signers
         # the notary's one long-lived key, expanded once on the engine's devices (cv_signer)
         self.key_pair = KeyPair(bytes(notary_seed), self.engine)
         self.public_key: EdDSAPublicKey = self.key_pair.public
@@ -240,6 +243,11 @@ class BatchingNotary:
             errs = self._verify(items)
             for k in range(n):
                 first_bad[k] = next((e for e in errs[begin[k]:begin[k + 1]] if e is not None), None)
+        missing: Dict[int, Optional[Exception]] = {}
+        if self.validating and self.device_signers:
+            ks = [k for k in range(n) if failed[k] is None and first_bad[k] is None]
+            missing = dict(zip(ks, missing_signatures_batch([requests[k].stx for k in ks], (self.owning_key,),
+                                                            self.engine)))
         accepted: List[int] = []
         conflicts: List[tuple] = []
         to_commit: List[tuple] = []
@@ -252,7 +260,11 @@ class BatchingNotary:
                 continue
             if self.validating:
                 e = first_bad[k]
-                if e is None:
+                if e is None and self.device_signers:
+                    if missing[k] is not None:
+                        results[k] = Result(False, error=SignaturesMissing(missing[k].missing))
+                        continue
+                elif e is None:
                     try:
                         r.stx._finish_verify((self.owning_key,))
                     except SignaturesMissingException as ex:

@@ -168,11 +168,150 @@ class SignedTransaction:
         return self.tx
 
 
+# ---------------------------------------------------------------- missing signers on the device (cv_missing_signers)
+def _device_decidable(key: CompositeKey) -> bool:
+    """Every Leaf of the tree holds a 32-byte EdDSAPublicKey (the device compares 32-byte records), and every Node is
+    one whose 32-bit evaluation is this mirror's: a weight per child, the threshold and every possible sum inside
+    Int (_Node.is_fulfilled_by sums in unbounded integers, the device wraps like the reference)."""
+    lim = 1 << 31
+    stack = [key]
+    while stack:
+        k = stack.pop()
+        if isinstance(k, CompositeKey.Leaf):
+            if not isinstance(k.public_key, EdDSAPublicKey):
+                return False
+        elif isinstance(k, CompositeKey.Node):
+            if len(k.weights) != len(k.children) or not -lim <= k.threshold < lim or sum(map(abs, k.weights)) >= lim:
+                return False
+            stack.extend(k.children)
+        else:
+            return False
+    return True
+
+
+def flatten_must_sign(stxs: Sequence[SignedTransaction], allowed: Iterable[CompositeKey] = ()) -> Dict[str, np.ndarray]:
+    """The flat encoding cv_missing_signers reads (include/cordaverify.h), by its argument names: every mustSign entry
+    of every transaction in post-order (children before parents, the root last; a subtree object met twice inside one
+    entry is emitted once and shared), the signer keys of every transaction, and req_allowed (the entry equals one
+    of `allowed`: CompositeKey equality is structural and stays on the host).  Keys are passed as the mirror compares
+    them, by their wire bytes (.encoded); a JVM binding passes getAbyte() on both sides.  Signers
+    that are not EdDSA keys equal no Leaf and are left out.  Every tree must be _device_decidable."""
+    allowed = set(allowed)
+    kind: List[int] = []
+    keys: List[bytes] = []
+    thr: List[int] = []
+    cb, child, weight, rb, trb, tsb = [0], [], [], [0], [0], [0]
+    sig: List[bytes] = []
+    req_allowed: List[int] = []
+    zero = bytes(32)
+    for stx in stxs:
+        for req in stx._wtx.must_sign:
+            if isinstance(req, CompositeKey.Leaf):                 # the common entry: one key
+                kind.append(native.CV_CK_LEAF); keys.append(req.public_key.encoded); thr.append(0)
+                cb.append(len(child)); rb.append(len(kind))
+                req_allowed.append(1 if req in allowed else 0)
+                continue
+            seen: Dict[int, int] = {}
+            # post-order without recursion: (node, visited)
+            stack = [(req, False)]
+            while stack:
+                k, visited = stack.pop()
+                if id(k) in seen:
+                    continue
+                if isinstance(k, CompositeKey.Leaf):
+                    seen[id(k)] = len(kind)
+                    kind.append(native.CV_CK_LEAF); keys.append(k.public_key.encoded); thr.append(0)
+                    cb.append(len(child))
+                elif not visited:
+                    stack.append((k, True))
+                    stack.extend((c, False) for c in reversed(k.children))
+                else:
+                    seen[id(k)] = len(kind)
+                    kind.append(native.CV_CK_NODE); keys.append(zero); thr.append(k.threshold)
+                    child.extend(seen[id(c)] for c in k.children)
+                    weight.extend(k.weights[:len(k.children)])
+                    cb.append(len(child))
+            rb.append(len(kind))
+            req_allowed.append(1 if req in allowed else 0)
+        trb.append(len(rb) - 1)
+        sig.extend(s.by.encoded for s in stx.sigs if isinstance(s.by, EdDSAPublicKey))
+        tsb.append(len(sig))
+    return {"kind": np.array(kind, np.uint8), "leaf_key": np.frombuffer(b"".join(keys), np.uint8).reshape(-1, 32),
+            "threshold": np.array(thr, np.int64).astype(np.int32), "child_begin": np.array(cb, np.uint32),
+            "child": np.array(child, np.uint32), "weight": np.array(weight, np.int64).astype(np.int32),
+            "req_begin": np.array(rb, np.uint32), "tx_req_begin": np.array(trb, np.uint32),
+            "sig_key": np.frombuffer(b"".join(sig), np.uint8).reshape(-1, 32), "tx_sig_begin": np.array(tsb, np.uint32),
+            "req_allowed": np.array(req_allowed, np.uint8)}
+
+
+def _missing_exception(stx: SignedTransaction, needed) -> Optional[SignaturesMissingException]:
+    """The SignaturesMissingException of _finish_verify for the needed (missing and not allowed) entries."""
+    if not needed:
+        return None
+    wtx = stx._wtx
+    descr = [d for k, d in wtx.command_descriptions.items() if k in needed]
+    if wtx.notary_key is not None and wtx.notary_key in needed:
+        descr.append("notary")
+    return SignaturesMissingException(needed, descr, stx.id)
+
+
+def missing_signatures_batch(stxs: Sequence[SignedTransaction], allowed_to_be_missing: Iterable[CompositeKey] = (),
+                             engine: Optional[native.Engine] = None) -> List[Optional[SignaturesMissingException]]:
+    """getMissingSignatures() minus allowedToBeMissing (SignedTransaction.kt:58-72, 89-93) for many transactions in
+    ONE device call (cv_missing_signers): per transaction None, or the SignaturesMissingException _finish_verify
+    raises — the same missing set, descriptions and id, built from req_missing and req_allowed, no is_fulfilled_by.
+    The id check of the `tx` getter stays with the caller.  A transaction whose must_sign holds a Leaf that is not
+    a 32-byte EdDSAPublicKey (DummyPublicKey, NullPublicKey) is decided on the host as before."""
+    allowed = set(allowed_to_be_missing)
+    out: List[Optional[SignaturesMissingException]] = [None] * len(stxs)
+    dev = []
+    for k, stx in enumerate(stxs):
+        if all(_device_decidable(r) for r in stx._wtx.must_sign):
+            dev.append(k)
+        else:
+            sig_keys = {s.by for s in stx.sigs}
+            missing = {r for r in stx._wtx.must_sign if not r.is_fulfilled_by(sig_keys)}
+            out[k] = _missing_exception(stx, missing - allowed)
+    if dev:
+        f = flatten_must_sign([stxs[k] for k in dev], allowed)
+        eng = engine or native.default_engine()
+        req_missing, _ = eng.missing_signers(**f)
+        if (req_missing > 1).any():
+            raise IllegalStateException("cv_missing_signers: the flattened mustSign trees came back malformed")
+        need = (req_missing == 1) & (f["req_allowed"] == 0)
+        trb = f["tx_req_begin"]
+        for j, k in enumerate(dev):
+            b, e = int(trb[j]), int(trb[j + 1])
+            if need[b:e].any():
+                ms = stxs[k]._wtx.must_sign
+                out[k] = _missing_exception(stxs[k], {ms[i] for i in range(e - b) if need[b + i]})
+    return out
+
+
+def _finish_verify_batch(stxs: Sequence[SignedTransaction], allowed, engine) -> List[Optional[Exception]]:
+    """_finish_verify for many transactions with the missing-signers decision on the device: the `tx` getter's id
+    check first (it is what _finish_verify reads the signers through), then missing_signatures_batch."""
+    out: List[Optional[Exception]] = [None] * len(stxs)
+    ok = []
+    for k, stx in enumerate(stxs):
+        try:
+            stx.tx
+            ok.append(k)
+        except Exception as e:  # noqa: BLE001 - mirrored reference exceptions
+            out[k] = e
+    for k, e in zip(ok, missing_signatures_batch([stxs[k] for k in ok], allowed, engine)):
+        out[k] = e
+    return out
+
+
 def verify_signatures_batch(stxs: Sequence[SignedTransaction], allowed_to_be_missing: Iterable[CompositeKey] = (),
-                            engine: Optional[native.Engine] = None) -> List[Optional[Exception]]:
+                            engine: Optional[native.Engine] = None, device_signers: bool = False
+                            ) -> List[Optional[Exception]]:
     """verifySignatures() over many transactions with ONE signature-verify call and ONE Merkle call
     (the ResolveTransactionsFlow / notary batch site).  Returns per transaction
-    None (verified) or the exception the sequential reference would raise for it."""
+    None (verified) or the exception the sequential reference would raise for it.  device_signers: the missing
+    signers of all transactions decided in ONE more device call (missing_signatures_batch) instead of one host
+    evaluation per transaction; the results are the same."""
     allowed = tuple(allowed_to_be_missing)
     items: List[VerifyItem] = []
     begin = [0]
@@ -183,6 +322,12 @@ def verify_signatures_batch(stxs: Sequence[SignedTransaction], allowed_to_be_mis
     unknown = [s._wtx for s in stxs if s._wtx._id is None]
     if unknown:
         compute_ids(unknown, engine)
+    if device_signers:
+        firsts = [next((e for e in errs[begin[k]:begin[k + 1]] if e is not None), None) for k in range(len(stxs))]
+        valid = [k for k, e in enumerate(firsts) if e is None]
+        for k, e in zip(valid, _finish_verify_batch([stxs[k] for k in valid], allowed, engine)):
+            firsts[k] = e
+        return firsts
     out: List[Optional[Exception]] = []
     for k, stx in enumerate(stxs):
         first = next((e for e in errs[begin[k]:begin[k + 1]] if e is not None), None)
@@ -198,7 +343,8 @@ def verify_signatures_batch(stxs: Sequence[SignedTransaction], allowed_to_be_mis
 
 
 def verify_signatures_batch_fused(stxs: Sequence[SignedTransaction], allowed_to_be_missing: Iterable[CompositeKey] = (),
-                                  engine: Optional[native.Engine] = None) -> List[Optional[Exception]]:
+                                  engine: Optional[native.Engine] = None, device_signers: bool = False
+                                  ) -> List[Optional[Exception]]:
     """verify_signatures_batch through ONE cv_verify_transactions call (every id recomputed on the device and
     kept there as its signatures' message), with the same per-transaction exceptions as the sequential reference.
 
@@ -213,7 +359,7 @@ def verify_signatures_batch_fused(stxs: Sequence[SignedTransaction], allowed_to_
       - no leaves (MerkleTreeException from `tx`) or a signature the host prefilter rejects (non-EdDSA key,
         wrong length): these never enter the fused call.
     Every honest transaction is decided by the fused call alone (INTEGRATION.md gives the JVM shim the same
-    rule)."""
+    rule).  device_signers: as verify_signatures_batch's."""
     allowed = tuple(allowed_to_be_missing)
     eng = engine or native.default_engine()
     fused, slow = [], []
@@ -260,6 +406,11 @@ def verify_signatures_batch_fused(stxs: Sequence[SignedTransaction], allowed_to_
             out[k] = next((e for e in errs[begin[j]:begin[j + 1]] if e is not None), None)
             if out[k] is None:
                 decided.append(k)
+    if device_signers:
+        decided.sort()
+        for k, e in zip(decided, _finish_verify_batch([stxs[k] for k in decided], allowed, eng)):
+            out[k] = e
+        return out
     for k in decided:
         try:
             stxs[k]._finish_verify(allowed)

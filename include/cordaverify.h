@@ -43,6 +43,11 @@
  *                                 InMemoryUniquenessProvider.kt:14-36 decides it (the decision half of
  *                                 PersistentUniquenessProvider.kt:61-81), for NotaryFlow.kt:133-141: a device-resident
  *                                 set of consumed states, a batch decided exactly as sequential commits would
+ *   cv_missing_signers        N x  SignedTransaction.getMissingSignatures() and the verdict verifySignatures draws from it
+ *                                 core/src/main/kotlin/net/corda/core/transactions/SignedTransaction.kt:58-72,89-93
+ *                                 (tx.mustSign.filter { !it.isFulfilledBy(sigKeys) } minus allowedToBeMissing) over
+ *                                 weighted-threshold CompositeKey trees, core/.../crypto/CompositeKey.kt:22-108
+ *                                 (Leaf.isFulfilledBy :49, Node.isFulfilledBy :75-81)
  *
  * Conventions
  *   - Return codes: CV_OK (0) or a negative CV_E* code; nothing throws, aborts or longjmps across
@@ -381,6 +386,65 @@ int cv_uniq_stats(cv_uniq *u, uint64_t *out, size_t nout);
  * signatures is not ok (SignedTransaction requires sigs.isNotEmpty(), SignedTransaction.kt:27-29). */
 int cv_tx_verdicts(size_t ntx, const uint64_t *verdict_bitmap, const uint32_t *tx_sig_begin, uint8_t *tx_ok);
 
+/* Missing signers: N x SignedTransaction.getMissingSignatures() (SignedTransaction.kt:89-93) with the verdict
+ * verifySignatures (SignedTransaction.kt:58-72) draws from it, CompositeKey.isFulfilledBy (CompositeKey.kt:49, 75-81)
+ * evaluated on the device for every mustSign entry of every transaction.
+ *   Semantics, the reference's.  sigKeys = the set of the transaction's signer keys.  A Leaf is fulfilled iff its key
+ *     is in sigKeys.  A Node is fulfilled iff the sum over its children of weights[i] where child i is fulfilled is >=
+ *     threshold: the sum is a Kotlin Int (32-bit two's complement, it WRAPS), the compare signed.  The 0.7 constructor
+ *     validates nothing: weights may be negative, a threshold <= 0 is fulfilled by nobody's signature, a Node without
+ *     children is fulfilled iff threshold <= 0, a child listed twice counts twice.
+ *   Key identity.  The call compares the 32 bytes it is given, all of them, and decodes nothing.  The reference
+ *     compares EdDSAPublicKeys by getAbyte(), the canonical re-encoding, not by the wire bytes (the wire key
+ *     ed ff .. ff 7f, y = p, re-encodes to 32 zero bytes).  The binding therefore passes getAbyte() for leaf keys and
+ *     signer keys alike.
+ *   Encoding.  The binding flattens each mustSign entry (a requirement) in post-order and concatenates them: node k
+ *     has kind[k] (CV_CK_LEAF / CV_CK_NODE), a Leaf its key leaf_key[k][32] (zero for a Node), a Node threshold[k]
+ *     (zero for a Leaf) and the children child[child_begin[k] .. child_begin[k+1]) (absolute node indices) with
+ *     weight[] beside them; a Leaf's child range is empty and is not read.  Requirement r is nodes [req_begin[r],
+ *     req_begin[r+1]), its root last; every child of node k lies in [req_begin[r], k).  A node may be the child of
+ *     several nodes: the encoding is a DAG that evaluates as the tree it unfolds to, so equal subtrees may be shared.
+ *     Transaction t owns requirements [tx_req_begin[t], tx_req_begin[t+1]) and the signer keys sig_key[tx_sig_begin[t]
+ *     .. tx_sig_begin[t+1])[32]; tx_sig_begin is the array cv_verify_transactions takes.
+ *   req_allowed[r] (NULL: none): non-zero when requirement r equals one of allowedToBeMissing.  CompositeKey equality
+ *     is structural and stays with the binding (a set lookup; the reference's callers pass nothing or one notary key).
+ *   verdict_bitmap (NULL: all valid): the verdict bits of the signatures, as cv_ed25519_verify_batch writes them.
+ *   req_missing[r]: 0 fulfilled; 1 missing — getMissingSignatures as it stands, whatever req_allowed and the bitmap
+ *     say; 2 malformed: a kind outside {0, 1}, a child range that descends or ends past nchild, a child index outside
+ *     [req_begin[r], k), an empty requirement.  Whatever the child arrays hold, no kernel reads outside a
+ *     requirement's own nodes or its transaction's own signer keys.  Equal requirements are each flagged.
+ *   tx_status[t], first match wins: CV_VS_MALFORMED if one of its requirements is malformed; CV_VS_BAD_SIGNATURE if it
+ *     has no signatures, or a bitmap is given and one of its bits is 0 (the rule of cv_tx_verdicts, and the
+ *     reference's precedence: checkSignaturesAreValid runs before the missing check); CV_VS_MISSING if some
+ *     req_missing[r] == 1 with req_allowed[r] == 0; else CV_VS_OK.  A transaction without requirements is never
+ *     CV_VS_MISSING.  Duplicate signer keys count once (sigKeys is a set).
+ *   wide_min: a transaction whose max(nodes, 1) x max(signers, 1) reaches it is decided by one wave (signer keys
+ *     staged through the LDS) instead of one lane; 0 = the default (4096), 1 = always, UINT32_MAX = never.  The
+ *     result never depends on it: tests force each path.  Either way the cost is nodes x signers first-word compares
+ *     (no hashing): the binding bounds the size of a transaction.
+ * Synchronous, on one device (the least loaded).  Before any device work: tx_req_begin, tx_sig_begin and req_begin
+ * with begin[0] == 0, monotone, the last entry equal to its count, child_begin[0] == 0 and child_begin[nnodes] ==
+ * nchild, no array missing that a non-zero count needs (CV_E_ARGS otherwise; what lies between child_begin's ends is
+ * checked per requirement on the device, so a bad tree fails its transaction and not the batch); a count above
+ * 0xfffffffe: CV_E_TOO_LARGE.  ntx == 0 returns CV_OK and writes nothing.  Outputs as under Conventions. */
+#define CV_CK_LEAF 0
+#define CV_CK_NODE 1
+#define CV_VS_OK 0
+#define CV_VS_BAD_SIGNATURE 1   /* no signatures, or (bitmap given) a signature's bit is 0 */
+#define CV_VS_MISSING 2         /* SignaturesMissingException: a requirement missing and not allowed */
+#define CV_VS_MALFORMED 3       /* a requirement of this transaction is not a tree encoding (no reference counterpart) */
+int cv_missing_signers(cv_ctx *ctx, size_t ntx, size_t nreq, size_t nnodes, size_t nchild, size_t nsig,
+                       const uint8_t *kind /* nnodes */, const uint8_t *leaf_key /* nnodes*32 */,
+                       const int32_t *threshold /* nnodes */, const uint32_t *child_begin /* nnodes+1 */,
+                       const uint32_t *child /* nchild */, const int32_t *weight /* nchild */,
+                       const uint32_t *req_begin /* nreq+1 */, const uint32_t *tx_req_begin /* ntx+1 */,
+                       const uint8_t *sig_key /* nsig*32 */, const uint32_t *tx_sig_begin /* ntx+1 */,
+                       const uint8_t *req_allowed /* nreq, NULL = none */,
+                       const uint64_t *verdict_bitmap /* ceil(nsig/64), NULL = all valid */, uint32_t wide_min,
+                       uint8_t *req_missing /* nreq */, uint8_t *tx_status /* ntx */);
+/* host only: the bytes of cv_missing_signers_device's d_workspace */
+uint64_t cv_missing_signers_workspace(size_t ntx, size_t nnodes);
+
 /* SignedTransaction.verifySignatures over a batch in one call (SignedTransaction.kt:59-71, 83-87 with
  * WireTransaction.id, WireTransaction.kt:45-52): the ids of ntx transactions (leaves as cv_merkle_tx_ids_ex) and
  * the verify of their signatures over those ids, the ids staying on the device as the messages.  The signatures
@@ -422,11 +486,13 @@ int cv_verify_transactions_ex(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena
  * that workspace), so concurrent calls serialise on the device instead of racing.
  * Alignment (the kernels' vector accesses need it; a pointer below it faults the GPU, nothing checks it):
  *     16 bytes  d_pk, d_sig, d_keys, d_seed (inputs and outputs: records are read and written as 16-byte vectors),
- *               d_ids, d_workspace
+ *               d_ids, d_workspace, d_leaf_key, d_sig_key
  *      8 bytes  d_bitmap (whole 64-bit words, 64-bit atomics), d_off, d_leaf_off
- *      4 bytes  d_len, d_leaf_len, d_key_index, d_tx_leaf_begin
+ *      4 bytes  d_len, d_leaf_len, d_key_index, d_tx_leaf_begin, and the 32-bit arrays of cv_missing_signers_device
+ *               (d_threshold, d_child_begin, d_child, d_weight, d_req_begin, d_tx_req_begin, d_tx_sig_begin)
  *      none     d_status, d_tx_status, d_arena (messages and leaves may start at any byte; the engine reads the
- *               aligned 32-bit words that hold their bytes, never a word that holds none)
+ *               aligned 32-bit words that hold their bytes, never a word that holds none), d_kind, d_req_allowed,
+ *               d_req_missing
  * Outputs as under Conventions: any prior contents, zero tail bits in d_bitmap, ceil(n/64) * 8 bytes of it written
  * and not one more, a zero id for an empty transaction; n == 0 (ntx == 0) enqueues nothing.
  */
@@ -470,6 +536,20 @@ int cv_ed25519_sign_keyed_device(cv_ctx *ctx, int device, const cv_signer *s, si
 int cv_merkle_tx_ids_device(cv_ctx *ctx, int device, size_t ntx, size_t nleaves, const void *d_arena,
                             const void *d_leaf_off, const void *d_leaf_len, const void *d_tx_leaf_begin,
                             void *d_workspace, void *d_ids, void *d_tx_status, void *stream);
+
+/* Device-resident form of cv_missing_signers (SignedTransaction.kt:58-72,89-93; CompositeKey.kt:49,75-81): the same
+ * arrays as device pointers, d_workspace of cv_missing_signers_workspace(ntx, nnodes) bytes (overwritten; nothing is
+ * expected in it).  Enqueues on `stream` and returns without synchronising or reading anything back, so it chains
+ * behind cv_ed25519_verify_device on the same stream and takes that call's d_bitmap as it stands.  It TRUSTS
+ * d_tx_req_begin, d_tx_sig_begin and d_req_begin (begin[0] == 0, monotone, the last entry equal to the count), as the
+ * other device-resident calls trust their ranges; everything per node, d_child_begin included, is checked on the device
+ * as in the host form.  d_req_allowed and d_bitmap may be NULL (none allowed; all valid). */
+int cv_missing_signers_device(cv_ctx *ctx, int device, size_t ntx, size_t nreq, size_t nnodes, size_t nchild, size_t nsig,
+                              const void *d_kind, const void *d_leaf_key, const void *d_threshold,
+                              const void *d_child_begin, const void *d_child, const void *d_weight,
+                              const void *d_req_begin, const void *d_tx_req_begin, const void *d_sig_key,
+                              const void *d_tx_sig_begin, const void *d_req_allowed, const void *d_bitmap,
+                              uint32_t wide_min, void *d_req_missing, void *d_tx_status, void *d_workspace, void *stream);
 
 /* Block until all work the context enqueued on `device` has finished. */
 int cv_synchronize(cv_ctx *ctx, int device);
