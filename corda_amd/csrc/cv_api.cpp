@@ -4,7 +4,8 @@
 // buffers) for plain, keyed, Merkle and transaction batches with synchronous and asynchronous forms, tickets, the
 // device-resident verify and Merkle entry points used by bench.py, and calibration.  The engine state is
 // cv_host.h's, the staging logic cv_stage.h's; signing (cv_api_sign.cpp), partial Merkle trees (cv_api_pmt.cpp)
-// and the uniqueness set (cv_api_uniq.cpp) are translation units of their own.
+// the uniqueness set (cv_api_uniq.cpp), missing signers (cv_api_ck.cpp) and the notary's fused call (cv_api_notary.cpp)
+// are translation units of their own.
 #include "cv_host.h"
 
 using namespace cvh;

@@ -53,14 +53,7 @@ int cv_ed25519_sign_batch(cv_ctx *ctx, size_t n, const uint8_t *seed, const uint
 }
 
 // ---------------------------------------------------------------- fixed-key signing (cv_signer)
-// One Ed25519 key expanded once per device of the context: rec[k] is device k's record (a | prefix | abyte,
-// CVK_SIGN_REC_BYTES), in the order of ctx->devs.  Immutable after cv_signer_open, so any number of threads
-// sign with it at once; the only host copy of key material is the public key.
-struct cv_signer {
-    cv_ctx *ctx = nullptr;
-    std::vector<void *> rec;
-    uint8_t pk[32] = {};
-};
+// struct cv_signer is cv_host.h's: cv_api_notary.cpp signs with the record of the uniqueness set's device.
 
 static void wipe(volatile uint8_t *p, size_t n) {
     for (size_t i = 0; i < n; i++) p[i] = 0;

@@ -1,5 +1,6 @@
-// cv_api_uniq.cpp — the device-resident uniqueness set of the C-ABI (include/cordaverify.h): struct cv_uniq and
-// the cv_uniq_* entry points.  The engine state is cv_host.h's.
+// cv_api_uniq.cpp — the device-resident uniqueness set of the C-ABI (include/cordaverify.h): the cv_uniq_* entry
+// points and the decision helpers cv_api_notary.cpp shares (cvh::uniq_*).  The engine state, struct cv_uniq included,
+// is cv_host.h's.
 #include "cv_host.h"
 
 using namespace cvh;
@@ -7,25 +8,6 @@ using namespace cvh;
 extern "C" {
 
 // ---------------------------------------------------------------- uniqueness set (the notary's commit step)
-// The set lives on one device of its context, with a stream, a workspace and a pinned read-back block of its own,
-// so its calls take no device lock: they serialise on the set's mutex (the reference's ThreadBox).  The table is
-// five arrays in ONE allocation (occ | key | id | index | caller, cv_uniq.h); growth builds a second one, rehashes on
-// the device and frees the first.
-struct cv_uniq {
-    cv_ctx *ctx = nullptr;
-    int ordinal = 0;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    void *tab = nullptr;
-    CvUniqTable T{};
-    size_t capacity = 0, resident = 0;
-    DevBuf ws, dstat;
-    uint32_t *hstat = nullptr;               // pinned: the device counters read back
-    int max_rounds = 8;
-    uint64_t last_rounds = 0, last_tail = 0, last_probe = 0, wraps = 0;
-};
-
-static const size_t kUniqMaxStates = (size_t)1 << 30;   // a table's slot count stays within 2^31
 
 static size_t uniq_slots(size_t capacity) {
     size_t s = 16;
@@ -59,8 +41,11 @@ static int uniq_alloc(size_t capacity, uint64_t seed, hipStream_t s, void **base
     return CV_OK;
 }
 
+}  // extern "C"
+
 // counters zeroed before a call's kernels / read back and folded into the set's statistics after them
-static int uniq_stat_begin(cv_uniq *u) {
+namespace cvh {
+int uniq_stat_begin(cv_uniq *u) {
     CV_TRY(hipMemsetAsync(u->dstat.p, 0, 4 * CVU_D_WORDS, u->stream));
     return CV_OK;
 }
@@ -69,13 +54,43 @@ static int uniq_stat_read(cv_uniq *u) {
     CV_TRY(hipStreamSynchronize(u->stream));
     return CV_OK;
 }
-static int uniq_stat_end(cv_uniq *u) {
+int uniq_stat_end(cv_uniq *u) {
     const int rc = uniq_stat_read(u);
     if (rc != CV_OK) return rc;
     u->last_probe = u->hstat[CVU_D_MAXPROBE];
     u->wraps += u->hstat[CVU_D_WRAPS];
     return u->hstat[CVU_D_ERROR] ? CV_E_HIP : CV_OK;            // a probe ran out of slots: never with the sizes above
 }
+
+uint32_t uniq_bmask(size_t nstates) {
+    size_t s = 16;
+    while (s < 2 * nstates) s <<= 1;
+    return (uint32_t)(s - 1);
+}
+
+// The decision of one batch on the set's stream: front, then rounds while the device says a request is undecided (one
+// 4-byte read-back per round), then the serial tail for what max_rounds left (with no round run the count is unknown
+// and the tail looks for itself), report + insert.  Shared by cv_uniq_commit_batch and cv_notarise_batch.
+int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, uint64_t *rounds_out) {
+    hipStream_t s = u->stream;
+    CV_TRY(cvk_uniq_front(&u->T, &B, cur, s));
+    uint64_t rounds = 0;
+    bool undecided = true;
+    while (undecided && rounds < (uint64_t)u->max_rounds) {
+        CV_TRY(cvk_uniq_round(&B, cur, nxt, (uint32_t)rounds, s));
+        std::swap(cur, nxt);
+        CV_TRY(hipMemcpyAsync(u->hstat, B.dstat + CVU_D_ROUND0 + rounds, 4, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipStreamSynchronize(s));
+        undecided = u->hstat[0] != 0;
+        rounds++;
+    }
+    CV_TRY(cvk_uniq_finish(&u->T, &B, cur, undecided ? 1 : 0, s));
+    *rounds_out = rounds;
+    return CV_OK;
+}
+}  // namespace cvh
+
+extern "C" {
 
 int cv_uniq_open(cv_ctx *ctx, int device, size_t capacity_states, cv_uniq **out) {
     if (out) *out = nullptr;
@@ -108,6 +123,9 @@ void cv_uniq_close(cv_uniq *u) {
     if (u->stream) (void)hipStreamSynchronize(u->stream);
     if (u->tab) (void)hipFree(u->tab);
     u->ws.release();
+    u->nws.release();
+    u->nin.release();
+    u->nout.release();
     u->dstat.release();
     if (u->hstat) (void)hipHostFree(u->hstat);
     if (u->stream) (void)hipStreamDestroy(u->stream);
@@ -165,12 +183,6 @@ static bool uniq_ranges_ok(size_t ntx, const uint32_t *begin) {
     for (size_t t = 0; t < ntx; t++)
         if (begin[t + 1] < begin[t]) return false;
     return true;
-}
-
-static uint32_t uniq_bmask(size_t nstates) {
-    size_t s = 16;
-    while (s < 2 * nstates) s <<= 1;
-    return (uint32_t)(s - 1);
 }
 
 int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const uint32_t *tx_state_begin,
@@ -231,21 +243,9 @@ int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const
     B.cons_index = u32(o_cix);
     B.cons_caller = u32(o_cc);
     B.dstat = u->dstat.as<uint32_t>();
-    uint32_t *cur = u32(o_s0), *nxt = u32(o_s1);
-    CV_TRY(cvk_uniq_front(&u->T, &B, cur, s));
-    // rounds while the device says a request is undecided (one 4-byte read-back per round), then the serial tail
-    // for what max_rounds left; with no round run the count is unknown and the tail looks for itself
     uint64_t rounds = 0;
-    bool undecided = true;
-    while (undecided && rounds < (uint64_t)u->max_rounds) {
-        CV_TRY(cvk_uniq_round(&B, cur, nxt, (uint32_t)rounds, s));
-        std::swap(cur, nxt);
-        CV_TRY(hipMemcpyAsync(u->hstat, B.dstat + CVU_D_ROUND0 + rounds, 4, hipMemcpyDeviceToHost, s));
-        CV_TRY(hipStreamSynchronize(s));
-        undecided = u->hstat[0] != 0;
-        rounds++;
-    }
-    CV_TRY(cvk_uniq_finish(&u->T, &B, cur, undecided ? 1 : 0, s));
+    rc = uniq_decide(u, B, u32(o_s0), u32(o_s1), &rounds);
+    if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(tx_status, base + o_ts, T, hipMemcpyDeviceToHost, s));
     if (S) {
         CV_TRY(hipMemcpyAsync(state_conflict, base + o_sc, S, hipMemcpyDeviceToHost, s));

@@ -3,7 +3,7 @@
 // statistics, routing (dispatch), and the short slot and workspace helpers (the longer ones — a slot's stream and
 // helper stream, its workspace growth, a verify launch group — serve the core alone and are file-local there).
 // Built on cv_stage.h (host staging, no devices) and cv_launch.h (the kernel launchers); included by cv_api.cpp
-// (the core) and the feature translation units cv_api_sign.cpp, cv_api_pmt.cpp, cv_api_uniq.cpp and cv_api_ck.cpp.  The types
+// (the core) and the feature translation units cv_api_sign.cpp, cv_api_pmt.cpp, cv_api_uniq.cpp, cv_api_ck.cpp and cv_api_notary.cpp.  The types
 // live in namespace cvh (cv_ctx, a global type of the public header, is made of them); nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -478,7 +478,48 @@ struct cv_ctx {
     }
 };
 
+// The fixed-key signer (cv_api_sign.cpp): one Ed25519 key expanded once per device of the context; rec[k] is device
+// k's record (a | prefix | abyte, CVK_SIGN_REC_BYTES), in the order of ctx->devs.  Immutable after cv_signer_open, so
+// any number of threads sign with it at once; the only host copy of key material is the public key.
+struct cv_signer {
+    cv_ctx *ctx = nullptr;
+    std::vector<void *> rec;
+    uint8_t pk[32] = {};
+};
+
+// The uniqueness set (cv_api_uniq.cpp).  It lives on one device of its context, with a stream, a workspace and a
+// pinned read-back block of its own, so its calls take no device lock: they serialise on the set's mutex (the
+// reference's ThreadBox).  The table is five arrays in ONE allocation (occ | key | id | index | caller, cv_uniq.h);
+// growth builds a second one, rehashes on the device and frees the first.
+struct cv_uniq {
+    cv_ctx *ctx = nullptr;
+    int ordinal = 0;
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    void *tab = nullptr;
+    CvUniqTable T{};
+    size_t capacity = 0, resident = 0;
+    cvh::DevBuf ws, dstat;
+    uint32_t *hstat = nullptr;               // pinned: the device counters read back
+    int max_rounds = 8;
+    uint64_t last_rounds = 0, last_tail = 0, last_probe = 0, wraps = 0;
+    // cv_notarise_batch (cv_api_notary.cpp): its inputs packed in pinned memory for one upload, its device copy of them
+    // with the pipeline's workspace and outputs behind, and the pinned block the outputs come back through
+    cvh::PinBuf nin, nout;
+    cvh::DevBuf nws;
+    std::unique_ptr<cvh::WorkerPool> pool;   // host threads that pack a large batch's inputs (created on the first one)
+};
+
 namespace cvh {
+
+constexpr size_t kUniqMaxStates = (size_t)1 << 30;   // a table's slot count stays within 2^31
+
+// cv_api_uniq.cpp, shared with cv_api_notary.cpp: the counters zeroed before a call's kernels / read back (a
+// synchronisation) and folded into the set's statistics after them, the batch table's mask, the decision itself
+int uniq_stat_begin(cv_uniq *u);
+int uniq_stat_end(cv_uniq *u);
+uint32_t uniq_bmask(size_t nstates);
+int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, uint64_t *rounds);
 
 inline Device *find_dev(cv_ctx *ctx, int device) {
     for (auto &d : ctx->devs)

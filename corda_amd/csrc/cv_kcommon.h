@@ -9,6 +9,7 @@
 //   cv_k_pmt.hip   partial Merkle tree build (tear-offs): count, scan, emit
 //   cv_k_uniq.hip  the notary's uniqueness set (cv_uniq.h): group, rounds, tail, report + insert, load, lookup, rehash
 //   cv_k_ck.hip    missing signers (cv_ck.h): one lane per transaction, one wave per large transaction
+//   cv_k_notary.hip the notary's fused commit step (cv_notary.h): gate, state-key gather, finalise + list, scatter
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +19,7 @@
 #include "cv_hsquad.h"
 #include "cv_uniq.h"
 #include "cv_ck.h"
+#include "cv_notary.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -181,6 +183,11 @@ __global__ void cv_uniq_rehash_kernel(CvUniqTable from, CvUniqTable to, uint32_t
 // missing signers (cv_k_ck.hip, cv_ck.h): the wide kernel's workgroups are one wave
 __global__ void cv_ck_narrow_kernel(CvCk C);
 __global__ void cv_ck_wide_kernel(CvCk C);
+// the notary's fused commit step (cv_k_notary.hip, cv_notary.h): the finalise kernel is ONE workgroup
+__global__ void cv_notary_gate_kernel(CvNotary N);
+__global__ void cv_notary_gather_kernel(CvNotary N);
+__global__ void cv_notary_final_kernel(CvNotary N, uint32_t *count);
+__global__ void cv_notary_scatter_kernel(uint32_t count, const uint32_t *list, const uint4 *sig, uint4 *out);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

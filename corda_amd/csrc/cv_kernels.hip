@@ -420,6 +420,33 @@ hipError_t cvk_ck(const CvCk *a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---- the notary's fused commit step (cv_notary.h).  Counts are at most 2^30 (the uniqueness set's bound).
+hipError_t cvk_notary_gate(const CvNotary *N, hipStream_t stream) {
+    if (!N || N->ntx == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_notary_gate_kernel, uniq_grid(N->ntx), dim3(CV_BLOCK), 0, stream, *N);
+    return hipGetLastError();
+}
+
+hipError_t cvk_notary_gather(const CvNotary *N, hipStream_t stream) {
+    if (!N) return hipErrorInvalidValue;
+    if (N->nstates == 0) return hipSuccess;
+    hipLaunchKernelGGL(cv_notary_gather_kernel, uniq_grid(N->nstates), dim3(CV_BLOCK), 0, stream, *N);
+    return hipGetLastError();
+}
+
+hipError_t cvk_notary_final(const CvNotary *N, uint32_t *count, hipStream_t stream) {
+    if (!N || N->ntx == 0 || !count) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_notary_final_kernel, dim3(1), dim3(CVN_SCAN_BLOCK), 0, stream, *N, count);
+    return hipGetLastError();
+}
+
+hipError_t cvk_notary_scatter(uint32_t count, const uint32_t *list, const uint8_t *sig, uint8_t *out, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(cv_notary_scatter_kernel, uniq_grid(4ull * count), dim3(CV_BLOCK), 0, stream, count, list,
+                       reinterpret_cast<const uint4 *>(sig), reinterpret_cast<uint4 *>(out));
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

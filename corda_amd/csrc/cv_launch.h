@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "cv_ck.h"
+#include "cv_notary.h"
 #include "cv_uniq.h"
 
 // Helper stream and events of one verify workspace slot, used by cvk_verify's drain overlap (a
@@ -98,6 +99,15 @@ hipError_t cvk_uniq_rehash(const CvUniqTable *from, const CvUniqTable *to, uint3
 // the list's counter cleared, the narrow kernel, then (unless wide_min is UINT32_MAX) the wide kernel over the list.
 // a->wide_min == 0 takes the default; count, list and flag point into the caller's workspace (cvck_ws_bytes).
 hipError_t cvk_ck(const CvCk *a, hipStream_t stream);
+// The notary's fused commit step (cv_notary.h; kernels in cv_k_notary.hip), every step enqueued on `stream`, nothing
+// synchronised.  gate: one lane per transaction -> pre, enable, first_bad.  gather: one lane per state -> key (between
+// the leaf kernel and the tree kernel: cvk_merkle with ntx == 0, then with nleaves == 0).  final: ONE workgroup ->
+// outcome, the ascending list of accepted transactions with their signing records, its length in *count.  scatter:
+// compact signature j -> out[list[j]] (64 bytes each; out zeroed by the caller).
+hipError_t cvk_notary_gate(const CvNotary *N, hipStream_t stream);
+hipError_t cvk_notary_gather(const CvNotary *N, hipStream_t stream);
+hipError_t cvk_notary_final(const CvNotary *N, uint32_t *count, hipStream_t stream);
+hipError_t cvk_notary_scatter(uint32_t count, const uint32_t *list, const uint8_t *sig, uint8_t *out, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

@@ -34,6 +34,11 @@ CV_VS_OK = 0
 CV_VS_BAD_SIGNATURE = 1
 CV_VS_MISSING = 2
 CV_VS_MALFORMED = 3
+# cv_notarise_batch outcome[t] (CV_NS_*)
+CV_NS_SUCCESS, CV_NS_EMPTY, CV_NS_ID_MISMATCH, CV_NS_TIMESTAMP_INVALID, CV_NS_TX_INVALID = 0, 1, 2, 3, 4
+CV_NS_BAD_KEY, CV_NS_SIGNATURES_MISSING, CV_NS_MALFORMED, CV_NS_CONFLICT = 5, 6, 7, 8
+NS_NO_SIG = 0xFFFFFFFF            # first_bad: no signature of the transaction settled its outcome
+NS_PRE_SIGNATURE, NS_PRE_KEY = 1, 2   # sig_pre: the host prefilter's SignatureException / InvalidKeyException
 CK_WIDE_DEFAULT, CK_WIDE_ALWAYS, CK_WIDE_NEVER = 0, 1, 0xFFFFFFFF      # cv_missing_signers' wide_min
 CV_UNIQ_STATS = ("resident", "capacity", "slots", "rounds", "tail", "probe", "wraps")   # CV_UNIQ_STAT_*
 
@@ -53,6 +58,7 @@ EXPORTED = (
     "cv_uniq_open", "cv_uniq_close", "cv_uniq_reserve", "cv_uniq_commit_batch", "cv_uniq_lookup", "cv_uniq_load",
     "cv_uniq_set_max_rounds", "cv_uniq_stats",
     "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
+    "cv_notarise_batch",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -195,6 +201,9 @@ def load():
         lib.cv_missing_signers_workspace.restype = ctypes.c_uint64
         lib.cv_missing_signers_device.argtypes = [_vp, ctypes.c_int] + [_sz] * 5 + [_vp] * 12 + [ctypes.c_uint32] + [_vp] * 4
         lib.cv_missing_signers_device.restype = ctypes.c_int
+        lib.cv_notarise_batch.argtypes = ([_vp, _vp, _vp, ctypes.c_int, _sz, _vp, ctypes.c_uint64] + [_vp] * 11 + [_sz] * 3 +
+                                          [_vp] * 19)
+        lib.cv_notarise_batch.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp]
         lib.cv_ed25519_sign_keyed.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed_device.argtypes = [_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -675,6 +684,75 @@ class Engine:
                                             ctypes.c_uint32(wide_min), _p(req_missing), _p(tx_status)),
                "cv_missing_signers")
         return req_missing[:nreq], tx_status[:ntx]
+
+    NOTARISE_OUTPUTS = ("outcome", "ids", "notary_sig", "first_bad", "req_missing", "state_conflict", "consumed_id",
+                        "consumed_index", "consumed_caller")
+
+    def notarise_batch(self, uniq: "UniquenessSet", signer: "Signer", arena, leaf_off, leaf_len, tx_leaf_begin,
+                       tx_input_count, claimed_id, caller, tx_pre=None, sigs=None, reqs=None, out=None) -> dict:
+        """cv_notarise_batch: the notary's commit step for a batch in one call (ids, signatures, missing signers, the
+        commit on `uniq`, the notary's signatures with `signer`).  Leaves as merkle_tx_ids; the states of transaction
+        t are its first tx_input_count[t] leaves; claimed_id (ntx,32) u8; caller u32[ntx]; tx_pre u8[ntx] or None.
+        sigs = (pk (nsig,32), sig (nsig,64), tx_sig_begin u32[ntx+1], sig_pre u8[nsig] or None) makes the call
+        validating, with reqs = the arrays of missing_signers up to sig_key, then req_allowed or None: (kind, leaf_key,
+        threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key, req_allowed).  sigs None: the simple
+        notary.  Returns a dict of NOTARISE_OUTPUTS (include/cordaverify.h).  out: arrays to write into by name; an
+        optional output given as None is passed as NULL and comes back None.  CvError -4 when the set would pass its
+        capacity: nothing changed and nothing written."""
+        def arr(a, dt, n, what, width=1):
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.size != n * width:
+                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
+            return a if a.size else np.zeros(width, dt)
+        ntx, arena, leaf_off, leaf_len, tx_leaf_begin = self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
+        tx_input_count = arr(tx_input_count, np.uint32, ntx, "tx_input_count")
+        claimed_id = arr(claimed_id, np.uint8, ntx, "claimed_id", 32)
+        caller = arr(caller, np.uint32, ntx, "caller")
+        if tx_pre is not None:
+            tx_pre = arr(tx_pre, np.uint8, ntx, "tx_pre")
+        ns = int(tx_input_count[:ntx].sum())
+        nreq = nnodes = nchild = 0
+        a_sig = [None] * 4
+        a_req = [None] * 10
+        if sigs is not None:
+            if reqs is None:
+                raise ValueError("a validating call needs the requirement arrays")
+            pk, sg, tsb, sig_pre = sigs
+            tsb = arr(tsb, np.uint32, ntx + 1, "tx_sig_begin")
+            nsig = int(tsb[-1])
+            kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key, req_allowed = reqs
+            tx_req_begin = arr(tx_req_begin, np.uint32, ntx + 1, "tx_req_begin")
+            req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32).reshape(-1)
+            child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32).reshape(-1)
+            nreq, nnodes = req_begin.size - 1, child_begin.size - 1
+            child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
+            nchild = child.size
+            if nreq < 0 or nnodes < 0:
+                raise ValueError("the begin arrays must have count + 1 entries")
+            a_sig = [arr(pk, np.uint8, nsig, "pk", 32), arr(sg, np.uint8, nsig, "sig", 64), tsb,
+                     None if sig_pre is None else arr(sig_pre, np.uint8, nsig, "sig_pre")]
+            a_req = [arr(kind, np.uint8, nnodes, "kind"), arr(leaf_key, np.uint8, nnodes, "leaf_key", 32),
+                     arr(threshold, np.int32, nnodes, "threshold"), child_begin,
+                     child if nchild else np.zeros(1, np.uint32), arr(weight, np.int32, nchild, "weight"), req_begin,
+                     tx_req_begin, arr(sig_key, np.uint8, nsig, "sig_key", 32),
+                     None if req_allowed is None else arr(req_allowed, np.uint8, nreq, "req_allowed")]
+        m, q = max(ns, 1), max(ntx, 1)
+        fresh = {"outcome": lambda: np.zeros(q, np.uint8), "ids": lambda: np.zeros((q, 32), np.uint8),
+                 "notary_sig": lambda: np.zeros((q, 64), np.uint8), "first_bad": lambda: np.zeros(q, np.uint32),
+                 "req_missing": lambda: np.zeros(max(nreq, 1), np.uint8), "state_conflict": lambda: np.zeros(m, np.uint8),
+                 "consumed_id": lambda: np.zeros((m, 32), np.uint8), "consumed_index": lambda: np.zeros(m, np.uint32),
+                 "consumed_caller": lambda: np.zeros(m, np.uint32)}
+        out = dict(out or {})
+        o = [out[k] if k in out else fresh[k]() for k in self.NOTARISE_OUTPUTS]
+        rc = self._lib.cv_notarise_batch(self._h, uniq._open(), signer._h, 1 if sigs is not None else 0, ntx, _p(arena),
+                                         arena.size, _p(leaf_off), _p(leaf_len), _p(tx_leaf_begin), _p(tx_input_count),
+                                         _p(claimed_id), _p(caller), _p(tx_pre), *[_p(a) for a in a_sig], nreq, nnodes,
+                                         nchild, *[_p(a) for a in a_req], *[_p(a) for a in o])
+        if rc == -3:
+            self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
+        _check(rc, "cv_notarise_batch")
+        cut = {"outcome": ntx, "ids": ntx, "notary_sig": ntx, "first_bad": ntx, "req_missing": nreq}
+        return {k: None if a is None else a[:cut.get(k, ns)] for k, a in zip(self.NOTARISE_OUTPUTS, o)}
 
     # ------------------------------------------------------------ device-resident API
     def missing_signers_device(self, device: int, ntx: int, nreq: int, nnodes: int, nchild: int, nsig: int, d_kind: int,

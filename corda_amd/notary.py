@@ -40,7 +40,8 @@ from .crypto import (CompositeKey, DigitalSignature, EdDSAPublicKey, IllegalArgu
                      InvalidKeyException, KeyPair, SignatureException, VerifyItem, _prefilter, verify_many,
                      verify_with_ecdsa)
 from .transactions import (MerkleTreeException, SecureHash, SignaturesMissingException, SignedTransaction,
-                           WireTransaction, compute_ids, missing_signatures_batch)
+                           WireTransaction, _device_decidable, _missing_exception, compute_ids, flatten_must_sign,
+                           missing_signatures_batch)
 
 
 # ---------------------------------------------------------------- timestamps (Structures.kt:412-423)
@@ -196,8 +197,16 @@ def verify_many_sharded(items: Sequence[VerifyItem], engine, group=None) -> List
 class BatchingNotary:
     def __init__(self, notary_seed: bytes, validating: bool = True, engine: Optional[native.Engine] = None,
                  uniqueness=None,
-                 timestamp_checker: Optional[TimestampChecker] = None, group=None, device_signers: bool = False):
+                 timestamp_checker: Optional[TimestampChecker] = None, group=None, device_signers: bool = False,
+                 fused: bool = False):
+        """fused=True: notarise() makes ONE cv_notarise_batch call per batch (ids, signatures, missing signers, the
+        commit and the notary's signatures on the device, the reference's precedence settled in the library) and one
+        further signing call for the conflict reports.  It needs a DeviceUniquenessProvider(leaf_keys=True) and no
+        process group.  In fused mode a request with explicit input_refs, or with a mustSign entry the device cannot
+        decide (transactions._device_decidable: a Leaf that is not a 32-byte EdDSA key, weights outside Int), raises
+        IllegalArgumentException: the states are the input leaves and every requirement is decided on the device."""
         self.engine = engine or native.default_engine()
+        self.fused = fused
         # the missing signers of a whole batch in one device call (transactions.missing_signatures_batch) instead of
         # one host evaluation per request; off by default, as the device uniqueness provider is
         self.device_signers = device_signers
@@ -209,6 +218,8 @@ class BatchingNotary:
         self.uniqueness = uniqueness if uniqueness is not None else InMemoryUniquenessProvider()
         self.timestamp_checker = timestamp_checker or TimestampChecker()
         self.group = group
+        if fused and (group is not None or not getattr(self.uniqueness, "leaf_keys", False)):
+            raise IllegalArgumentException("fused=True needs a DeviceUniquenessProvider(leaf_keys=True) and no process group")
 
     def _verify(self, items: List[VerifyItem]) -> List[Optional[Exception]]:
         if self.group is not None:
@@ -219,8 +230,107 @@ class BatchingNotary:
         """The notary key over every message, in one GPU signing call (the fixed-key signer)."""
         return self.key_pair.sign_many(msgs)
 
+    def _notarise_fused(self, requests: Sequence[SignRequest]) -> List[Result]:
+        """notarise() through cv_notarise_batch: the batch flattened once, keys and lengths prefiltered into sig_pre,
+        TimestampChecker into tx_pre, one call, then the same Result objects as the unfused path."""
+        n = len(requests)
+        for r in requests:
+            if r.input_refs is not None:
+                raise IllegalArgumentException("fused notary: the states are the transaction's input leaves (input_refs given)")
+            if self.validating and not all(_device_decidable(k) for k in r.stx._wtx.must_sign):
+                raise IllegalArgumentException("fused notary: a mustSign entry that the device cannot decide")
+        leaves: List[bytes] = []
+        txb, nin = [0], []
+        for r in requests:
+            leaves.extend(r.stx._wtx.leaves)
+            txb.append(len(leaves))
+            nin.append(len(r.stx._wtx.inputs))
+        lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
+        offs = np.zeros(len(leaves), np.uint64)
+        if len(leaves) > 1:
+            offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+        claimed = np.frombuffer(b"".join(r.stx.id.bytes for r in requests), np.uint8)
+        tx_pre = np.array([1 if r.timestamp is not None and not self.timestamp_checker.is_valid(r.timestamp) else 0
+                           for r in requests], np.uint8)
+        sigs = reqs = None
+        pre_err: Dict[int, Exception] = {}
+        if self.validating:
+            pk, sg, sig_pre, tsb = [], [], [], [0]
+            zero32, zero64 = bytes(32), bytes(64)
+            for r in requests:
+                for s in r.stx.sigs:
+                    e = _prefilter(VerifyItem(s.by, r.stx.id.bytes, s.bits))
+                    if e is not None:
+                        pre_err[len(pk)] = e
+                    bad_key = isinstance(e, InvalidKeyException)
+                    pk.append(zero32 if bad_key else s.by.encoded)
+                    sg.append(zero64 if e is not None else bytes(s.bits))
+                    sig_pre.append(native.NS_PRE_KEY if bad_key else native.NS_PRE_SIGNATURE if e is not None else 0)
+                tsb.append(len(pk))
+            keys = np.frombuffer(b"".join(pk), np.uint8).reshape(-1, 32)
+            f = flatten_must_sign([r.stx for r in requests], (self.owning_key,))
+            sigs = (keys, np.frombuffer(b"".join(sg), np.uint8).reshape(-1, 64), np.array(tsb, np.uint32),
+                    np.array(sig_pre, np.uint8))
+            reqs = tuple(f[k] for k in ("kind", "leaf_key", "threshold", "child_begin", "child", "weight", "req_begin",
+                                        "tx_req_begin")) + (keys, f["req_allowed"])
+
+        def call(uniq, handles):
+            out = self.engine.notarise_batch(uniq, self.key_pair._signer, arena, offs, lens, np.array(txb, np.uint32),
+                                             np.array(nin, np.uint32), claimed, handles, tx_pre, sigs=sigs, reqs=reqs)
+            rows = [(state, requests[k].stx.id.bytes, i, requests[k].caller)
+                    for k in np.flatnonzero(out["outcome"] == native.CV_NS_SUCCESS)
+                    for i, state in enumerate(requests[k].stx._wtx.inputs)]
+            return out, rows                   # the provider appends the rows to its log before any signature is released
+
+        out, parties = self.uniqueness.fused([r.caller for r in requests], int(sum(nin)), call)
+        outcome = out["outcome"]
+        if (outcome == native.CV_NS_MALFORMED).any():
+            raise IllegalStateException("cv_notarise_batch: the flattened mustSign trees came back malformed")
+        results: List[Optional[Result]] = [None] * n
+        conflicts: List[tuple] = []
+        sbeg = np.concatenate([[0], np.cumsum(nin)])
+        for k, r in enumerate(requests):
+            o, w = int(outcome[k]), r.stx._wtx
+            if o != native.CV_NS_EMPTY and w._id is None:
+                w._id = SecureHash(out["ids"][k].tobytes())
+            if o == native.CV_NS_SUCCESS:
+                results[k] = Result(True, sig=DigitalSignature.WithKey(self.public_key, out["notary_sig"][k].tobytes()))
+            elif o == native.CV_NS_EMPTY:
+                results[k] = Result(False, failure=MerkleTreeException("Cannot calculate Merkle root on empty hash list."))
+            elif o == native.CV_NS_ID_MISMATCH:
+                try:
+                    r.stx.tx
+                    raise IllegalStateException("cv_notarise_batch: an id mismatch the mirror does not see")
+                except IllegalStateException as e:
+                    results[k] = Result(False, failure=e)
+            elif o == native.CV_NS_TIMESTAMP_INVALID:
+                results[k] = Result(False, error=TimestampInvalid())
+            elif o == native.CV_NS_TX_INVALID:
+                results[k] = Result(False, error=TransactionInvalid())
+            elif o == native.CV_NS_BAD_KEY:
+                i = int(out["first_bad"][k])
+                results[k] = Result(False, failure=pre_err.get(i) or InvalidKeyException("not a valid GroupElement"))
+            elif o == native.CV_NS_SIGNATURES_MISSING:
+                b, e = int(reqs[7][k]), int(reqs[7][k + 1])
+                need = {w.must_sign[i] for i in range(e - b) if out["req_missing"][b + i] == 1 and not reqs[9][b + i]}
+                results[k] = Result(False, error=SignaturesMissing(_missing_exception(r.stx, need).missing))
+            else:                                                  # CV_NS_CONFLICT
+                b = int(sbeg[k])
+                c = UniquenessConflict({s: ConsumingTx(SecureHash(out["consumed_id"][b + j].tobytes()),
+                                                       int(out["consumed_index"][b + j]),
+                                                       parties[int(out["consumed_caller"][b + j])])
+                                        for j, s in enumerate(w.inputs) if out["state_conflict"][b + j]})
+                conflicts.append((k, c.serialize()))
+        csigs = self._sign([raw for _, raw in conflicts]) if conflicts else []
+        for (k, raw), sig in zip(conflicts, csigs):
+            results[k] = Result(False, error=Conflict(requests[k].stx.tx, SignedData(raw, sig)))
+        return results  # type: ignore[return-value]
+
     def notarise(self, requests: Sequence[SignRequest]) -> List[Result]:
         n = len(requests)
+        if self.fused:
+            return self._notarise_fused(requests) if n else []
         results: List[Optional[Result]] = [None] * n
         # val wtx = stx.tx: every unknown id in one Merkle call, then check(temp.id == id) per request
         unknown = [r.stx._wtx for r in requests if r.stx._wtx._id is None]

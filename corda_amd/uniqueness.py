@@ -239,10 +239,18 @@ class DeviceUniquenessProvider:
     The device set is not durable.  With log= a PersistentUniquenessProvider, the set is loaded from the log's rows
     at start, and each batch's accepted rows are appended to the log in one durable transaction before the call
     returns — no SELECT: the device has already decided.  If that append fails the error is raised and the provider
-    refuses further work: the set then holds states the log does not, and has to be rebuilt from the log."""
+    refuses further work: the set then holds states the log does not, and has to be rebuilt from the log.
 
-    def __init__(self, engine, capacity: int = 1 << 16, log: Optional[PersistentUniquenessProvider] = None):
+    leaf_keys=True keys the set by the SHA-256 of the raw state bytes — for a notary whose states are the serialised
+    input leaves that is the input's Merkle leaf hash, the C-ABI's documented key (include/cordaverify.h, cv_uniq) and
+    the one cv_notarise_batch takes from the leaf hashes on the device.  States must then be bytes.  The fused notary
+    (notary.BatchingNotary(fused=True)) needs such a provider and drives it through fused(): the party handles, room
+    reserved before the call, and the log append of the accepted rows."""
+
+    def __init__(self, engine, capacity: int = 1 << 16, log: Optional[PersistentUniquenessProvider] = None,
+                 leaf_keys: bool = False):
         from . import native
+        self.leaf_keys = bool(leaf_keys)
         self._lock = threading.Lock()
         self._parties: List[str] = []
         self._handle: Dict[str, int] = {}
@@ -255,7 +263,7 @@ class DeviceUniquenessProvider:
                                        f"requesting_party_name FROM {log.TABLE}").fetchall()
         self._set = native.UniquenessSet(engine, max(int(capacity), 2 * len(rows), 1))
         if rows:
-            self._set.load(np.frombuffer(b"".join(self._key(bytes(r[0])) for r in rows), np.uint8),
+            self._set.load(np.frombuffer(b"".join(self._row_key(bytes(r[0])) for r in rows), np.uint8),
                            np.frombuffer(b"".join(bytes(r[1]) for r in rows), np.uint8),
                            np.array([int(r[2]) for r in rows], np.uint32),
                            np.array([self._party(r[3]) for r in rows], np.uint32))
@@ -263,6 +271,56 @@ class DeviceUniquenessProvider:
     @staticmethod
     def _key(enc: bytes) -> bytes:
         return hashlib.sha256(enc).digest()
+
+    def _state_key(self, state, enc: bytes) -> bytes:
+        if not self.leaf_keys:
+            return self._key(enc)
+        if not isinstance(state, (bytes, bytearray)):
+            raise TypeError("leaf_keys: a state is the bytes of its serialised input leaf")
+        return hashlib.sha256(bytes(state)).digest()
+
+    def _row_key(self, enc: bytes) -> bytes:
+        """The set's key of a log row (the log stores _enc(state))."""
+        return self._state_key(_dec(enc, 0)[0], enc) if self.leaf_keys else self._key(enc)
+
+    def _append(self, rows) -> None:
+        """The accepted rows (_enc(state), tx id bytes, input index, caller name) into the log, in one durable
+        transaction; a failure marks the provider broken (the set is then ahead of its log).  Caller holds the lock."""
+        if self._log is None:
+            return
+        try:
+            with self._log._lock:
+                db = self._log._db
+                db.execute("BEGIN IMMEDIATE")
+                try:
+                    db.executemany(f"INSERT OR REPLACE INTO {self._log.TABLE} VALUES (?, ?, ?, ?)", rows)
+                    db.execute("COMMIT")
+                except BaseException:
+                    if db.in_transaction:
+                        try:
+                            db.execute("ROLLBACK")
+                        except Exception:  # noqa: BLE001 - the original exception is the one to report
+                            pass
+                    raise
+        except BaseException:
+            self._broken = True
+            raise
+
+    def fused(self, callers: Sequence[str], nstates: int, call):
+        """What notary.BatchingNotary(fused=True) needs around ONE cv_notarise_batch, under the provider's lock: the
+        callers' party handles, room for nstates more states reserved beforehand, then call(uniqueness set, handles)
+        -> (result, accepted rows for the log), the rows appended durably before the result is released.  Returns
+        (result, party names by handle)."""
+        with self._lock:
+            if self._broken:
+                raise RuntimeError("the device set is ahead of its log: rebuild it from the log")
+            handles = np.array([self._party(c) for c in callers], np.uint32)
+            st = self._set.stats()
+            if st["resident"] + nstates > st["capacity"]:
+                self._set.reserve(max(2 * st["capacity"], st["resident"] + nstates))
+            result, rows = call(self._set, handles)
+            self._append([(_enc(s), t, i, c) for s, t, i, c in rows])
+            return result, list(self._parties)
 
     def _party(self, name: str) -> int:
         h = self._handle.get(name)
@@ -279,7 +337,7 @@ class DeviceUniquenessProvider:
 
     def get(self, state) -> Optional[ConsumingTx]:
         with self._lock:
-            found, cid, cix, cc = self._set.lookup(np.frombuffer(self._key(_enc(state)), np.uint8))
+            found, cid, cix, cc = self._set.lookup(np.frombuffer(self._state_key(state, _enc(state)), np.uint8))
             return ConsumingTx(SecureHash(cid[0].tobytes()), int(cix[0]), self._parties[int(cc[0])]) if found[0] else None
 
     def commit_batch(self, requests: Sequence[CommitRequest]) -> List[Optional[UniquenessConflict]]:
@@ -289,7 +347,8 @@ class DeviceUniquenessProvider:
         begin = np.zeros(len(requests) + 1, np.uint32)
         np.cumsum([len(e) for e in encs], out=begin[1:])
         ns = int(begin[-1])
-        keys = np.frombuffer(b"".join(self._key(e) for es in encs for e in es), np.uint8)
+        keys = np.frombuffer(b"".join(self._state_key(s, e) for (states, _, _), es in zip(requests, encs)
+                                      for s, e in zip(states, es)), np.uint8)
         ids = np.frombuffer(b"".join(t.bytes for _, t, _ in requests), np.uint8)
         with self._lock:
             if self._broken:
@@ -300,25 +359,8 @@ class DeviceUniquenessProvider:
                 self._set.reserve(max(2 * st["capacity"], st["resident"] + ns))
             status, conflict, cid, cix, cc = self._set.commit_batch(keys, begin, ids, callers)
             if self._log is not None:
-                rows = [(e, t.bytes, i, c) for (_, t, c), es, ok in zip(requests, encs, status == 0) if ok
-                        for i, e in enumerate(es)]
-                try:
-                    with self._log._lock:
-                        db = self._log._db
-                        db.execute("BEGIN IMMEDIATE")
-                        try:
-                            db.executemany(f"INSERT OR REPLACE INTO {self._log.TABLE} VALUES (?, ?, ?, ?)", rows)
-                            db.execute("COMMIT")
-                        except BaseException:
-                            if db.in_transaction:
-                                try:
-                                    db.execute("ROLLBACK")
-                                except Exception:  # noqa: BLE001 - the original exception is the one to report
-                                    pass
-                            raise
-                except BaseException:
-                    self._broken = True
-                    raise
+                self._append([(e, t.bytes, i, c) for (_, t, c), es, ok in zip(requests, encs, status == 0) if ok
+                              for i, e in enumerate(es)])
             parties = list(self._parties)
         out: List[Optional[UniquenessConflict]] = []
         for t, (states, _, _) in enumerate(requests):

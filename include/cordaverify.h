@@ -48,6 +48,11 @@
  *                                 (tx.mustSign.filter { !it.isFulfilledBy(sigKeys) } minus allowedToBeMissing) over
  *                                 weighted-threshold CompositeKey trees, core/.../crypto/CompositeKey.kt:22-108
  *                                 (Leaf.isFulfilledBy :49, Node.isFulfilledBy :75-81)
+ *   cv_notarise_batch         N x  NotaryFlow.Service.call with ValidatingNotaryFlow.beforeCommit's signature checks
+ *                                 core/src/main/kotlin/net/corda/flows/NotaryFlow.kt:96-146, ValidatingNotaryFlow.kt:24-45,
+ *                                 SignedTransaction.kt:34-38,58-93: ids, signatures, missing signers, the commit and
+ *                                 the notary's signatures for a whole batch in one call, the reference's outcome and
+ *                                 precedence settled in the library
  *
  * Conventions
  *   - Return codes: CV_OK (0) or a negative CV_E* code; nothing throws, aborts or longjmps across
@@ -473,6 +478,91 @@ int cv_verify_transactions_ex(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena
                               const uint64_t *leaf_off, const uint32_t *leaf_len, const uint32_t *tx_leaf_begin,
                               const uint8_t *pk, const uint8_t *sig, const uint32_t *tx_sig_begin, uint8_t *ids,
                               uint8_t *tx_status, uint8_t *sig_status, uint8_t *tx_ok, uint64_t *ticket);
+
+/* The notary's commit step for a whole batch in ONE call: N x NotaryFlow.Service.call (core/src/main/kotlin/net/corda/
+ * flows/NotaryFlow.kt:96-146) with, when `validating`, the signature checks of ValidatingNotaryFlow.beforeCommit
+ * (ValidatingNotaryFlow.kt:24-45; SignedTransaction.kt:34-38 `tx`, 58-93 verifySignatures, checkSignaturesAreValid,
+ * getMissingSignatures).  It is the composition of cv_merkle_tx_ids_bounded, cv_ed25519_verify_batch over the ids,
+ * cv_missing_signers (with the verify's bitmap), cv_uniq_commit_batch and cv_ed25519_sign_keyed, result for result, with
+ * the decisions between them made on the device: one upload, one read-back.  Contract verification and dependency
+ * resolution stay out of scope, as for the calls it is made of.
+ *   Transactions.  Leaves as cv_merkle_tx_ids_bounded (tx_leaf_begin[0] == 0, monotone; a leaf past
+ *     leaf_arena[leaf_arena_bytes), or one whose off + len wraps: CV_E_ARGS before any read).  claimed_id[t] is
+ *     SignedTransaction.id, caller[t] the requesting party's handle (cv_uniq), tx_pre[t] non-zero when the host's
+ *     TimestampChecker found the timestamp invalid (the leaves are not decoded here).
+ *   State keys.  The states of transaction t are its first tx_input_count[t] leaves (inputs come first in
+ *     WireTransaction's leaf order); a state's key is that leaf's SHA-256 digest, the documented key of cv_uniq, taken
+ *     from the leaf hashes the id is built from: not hashed again and not uploaded.  nstates = the sum of
+ *     tx_input_count; state i of the outputs counts the states of the transactions in order.  tx_input_count[t] above
+ *     the transaction's leaf count: CV_E_ARGS.
+ *   outcome[t], first match wins, in the reference's order:
+ *     1. CV_NS_EMPTY, then CV_NS_ID_MISMATCH: `val wtx = stx.tx` (NotaryFlow.kt:99) recomputes the id and checks it
+ *        against the claimed one OUTSIDE the try, so either fails the flow instead of answering with a NotaryError.
+ *     2. CV_NS_TIMESTAMP_INVALID: validateTimestamp (NotaryFlow.kt:102,115-119), tx_pre.
+ *     3. validating only (a non-validating notary's beforeCommit is empty, NotaryFlow.kt:129-131: it commits
+ *        transactions with bad signatures).  checkSignaturesAreValid (SignedTransaction.kt:82-87) throws at the FIRST
+ *        signature, in order, that fails — here: sig_pre[i] != 0 or a zero verdict bit — and that signature settles
+ *        the class: CV_NS_BAD_KEY (InvalidKeyException, re-thrown by ValidatingNotaryFlow.kt:34: the flow fails) when
+ *        sig_pre[i] == 2, or sig_pre[i] == 0 and the device status is CV_SIG_BAD_KEY; CV_NS_TX_INVALID
+ *        (SignatureException -> NotaryError.TransactionInvalid) otherwise.  A transaction without signatures is
+ *        CV_NS_TX_INVALID, the rule of cv_tx_verdicts.  Then the missing-signers verdict of cv_missing_signers over
+ *        the same batch (default wide_min; req_allowed honoured, duplicate signer keys counted once): CV_NS_MALFORMED,
+ *        CV_NS_SIGNATURES_MISSING (req_missing says which).
+ *     4. CV_NS_CONFLICT or CV_NS_SUCCESS from the uniqueness set, for the transactions that passed everything above,
+ *        and only for those.
+ *   The signatures are verified over the RECOMPUTED id, which stays on the device as the message.  A transaction that
+ *     reaches step 3 has recomputed id == claimed id, so this is the reference's verify over the claimed id
+ *     (SignedTransaction.kt:85) for every transaction whose signatures decide anything.
+ *   first_bad[t] (optional): the absolute index of the signature that settled CV_NS_TX_INVALID / CV_NS_BAD_KEY,
+ *     0xffffffff for every other transaction (one without signatures included, and all when not validating).
+ *   req_missing (optional): cv_missing_signers' req_missing for every requirement of the batch, whatever the outcome.
+ *   The commit is cv_uniq_commit_batch's, result for result, with tx_enable[t] = (nothing of steps 1-3 matched) and
+ *     tx_id = the id: decided as sequential commits in request order; a gated-out transaction commits nothing and
+ *     conflicts with nothing; state_conflict and consumed_* are that call's (zero for states without a conflict, and
+ *     for every state of a transaction that is not CV_NS_CONFLICT); CV_E_OOM before any change and any output when
+ *     resident + nstates > capacity.  Durability stays with the binding: it appends the accepted rows to its log
+ *     before it releases a signature.
+ *   notary_sig[t] = cv_ed25519_sign_keyed(s) over the 32 id bytes when outcome[t] == CV_NS_SUCCESS, 64 zero bytes
+ *     otherwise.  The signing kernel runs for the accepted transactions alone: a signature over the id of a
+ *     transaction that was not committed reaches no host-visible buffer.  Conflict reports (e.error.serialize() and
+ *     sign(conflictData), NotaryFlow.kt:136-139) stay with the binding: it serialises them from the records and signs
+ *     them with cv_ed25519_sign_keyed.
+ *   Not validating: pk .. sig_pre and nreq .. req_allowed are ignored and may be NULL / 0; first_bad is all
+ *     0xffffffff, req_missing is not written (there are no requirements).
+ * Synchronous, on the set's device, serialised on the set's mutex; `u` and `s` must belong to `ctx` (CV_E_ARGS).
+ * Before any device work: the range arrays as the component calls check them (begin[0] == 0, monotone, tx_req_begin
+ * ends at nreq, req_begin at nnodes, child_begin[0] == 0 and child_begin[nnodes] == nchild), no array missing that a
+ * non-zero count needs: CV_E_ARGS; a count above 0xfffffffe, or more than 2^30 transactions or states:
+ * CV_E_TOO_LARGE.  ntx == 0 returns CV_OK and touches nothing.  Outputs as under Conventions. */
+#define CV_NS_SUCCESS            0  /* committed; notary_sig[t] = signature over the id                      */
+#define CV_NS_EMPTY              1  /* no leaves: MerkleTreeException, the flow fails                        */
+#define CV_NS_ID_MISMATCH        2  /* recomputed id != claimed id: IllegalStateException, the flow fails    */
+#define CV_NS_TIMESTAMP_INVALID  3  /* NotaryError.TimestampInvalid                                          */
+#define CV_NS_TX_INVALID         4  /* first bad signature is a SignatureException: TransactionInvalid       */
+#define CV_NS_BAD_KEY            5  /* first bad signature is an InvalidKeyException: the flow fails         */
+#define CV_NS_SIGNATURES_MISSING 6  /* NotaryError.SignaturesMissing (req_missing says which)                */
+#define CV_NS_MALFORMED          7  /* a requirement is not a tree encoding (CV_VS_MALFORMED)                */
+#define CV_NS_CONFLICT           8  /* NotaryError.Conflict (state_conflict / consumed_* say with what)      */
+int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *s, int validating, size_t ntx,
+    /* transactions: leaves as cv_merkle_tx_ids_bounded */
+    const uint8_t *leaf_arena, uint64_t leaf_arena_bytes, const uint64_t *leaf_off, const uint32_t *leaf_len,
+    const uint32_t *tx_leaf_begin /* ntx+1 */, const uint32_t *tx_input_count /* ntx */,
+    const uint8_t *claimed_id /* ntx*32 */, const uint32_t *caller /* ntx */,
+    const uint8_t *tx_pre /* ntx, NULL = none: non-zero = the host's TimestampChecker said invalid */,
+    /* signatures (validating only; ignored and may be NULL otherwise) */
+    const uint8_t *pk /* nsig*32 */, const uint8_t *sig /* nsig*64 */, const uint32_t *tx_sig_begin /* ntx+1 */,
+    const uint8_t *sig_pre /* nsig, NULL = none: 1 = host prefilter SignatureException (bad length),
+                                                  2 = host prefilter InvalidKeyException (not EdDSA) */,
+    /* mustSign requirements, exactly the arrays of cv_missing_signers (validating only) */
+    size_t nreq, size_t nnodes, size_t nchild, const uint8_t *kind, const uint8_t *leaf_key,
+    const int32_t *threshold, const uint32_t *child_begin, const uint32_t *child, const int32_t *weight,
+    const uint32_t *req_begin, const uint32_t *tx_req_begin, const uint8_t *sig_key, const uint8_t *req_allowed,
+    /* outputs */
+    uint8_t *outcome /* ntx */, uint8_t *ids /* ntx*32, optional */, uint8_t *notary_sig /* ntx*64 */,
+    uint32_t *first_bad /* ntx, optional: absolute index of the first failing signature, 0xffffffff = none */,
+    uint8_t *req_missing /* nreq, optional */, uint8_t *state_conflict /* nstates */,
+    uint8_t *consumed_id /* nstates*32 */, uint32_t *consumed_index /* nstates */,
+    uint32_t *consumed_caller /* nstates */);
 
 /* ---------------------------------------------------------------- device-resident API
  * All pointers are device pointers on HIP device `device` (which must be in the context); work is
