@@ -388,8 +388,9 @@ static int key_resolve(Device &d, uint32_t cap, size_t nk, const uint8_t *keys, 
             continue;
         }
         auto f = fresh.find(key);
-        if (f != fresh.end()) {                   // a key repeated inside this call's key list
-            slot_of_key[k] = f->second;
+        if (f != fresh.end()) {                   // a key repeated inside this call's key list: a hit on the
+            slot_of_key[k] = f->second;           // slot its first row took (hits + misses = rows looked up)
+            kc.hits++;
             continue;
         }
         const uint32_t slot = next++;

@@ -183,7 +183,10 @@ int cv_ed25519_verify_batch_keyed(cv_ctx *ctx, size_t n, size_t nkeys, const uin
  * new keys go in; a call with more distinct keys than the capacity grows the pool to fit them. */
 int cv_key_cache_reserve(cv_ctx *ctx, size_t max_keys);
 
-/* out4 = {resident keys, capacity, lookups that hit, lookups that missed} for `device`. */
+/* out4 = {resident keys, capacity, lookups that hit, lookups that missed} for `device`.  One lookup per key
+ * row of a call: every row of the device-resident call's d_keys, and of the host-buffer calls the rows that some
+ * signature of the shard references (the others are never read).  A key already resident hits; of the rows of one
+ * call that hold the same new key, the first misses (its tables are computed once) and the others hit. */
 int cv_key_cache_stats(cv_ctx *ctx, int device, uint64_t *out4);
 
 int cv_merkle_tx_ids(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, const uint64_t *leaf_off,
