@@ -255,6 +255,8 @@ void cv_close(cv_ctx *ctx) {
         d.pin_out.release();
         d.zc_in.release();
         d.zc_out.release();
+        d.ts_in.release();
+        d.ts_out.release();
         for (int k = 0; k < kSlots; k++) {
             Slot &sl = d.slot[k];
             for (DevBuf *b : {&sl.ws_hs, &sl.ws_tab, &sl.ws_R, &sl.ws_ok, &sl.ws_dig, &sl.mdig, &sl.packed, &sl.head})

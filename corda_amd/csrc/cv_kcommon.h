@@ -10,6 +10,7 @@
 //   cv_k_uniq.hip  the notary's uniqueness set (cv_uniq.h): group, rounds, tail, report + insert, load, lookup, rehash
 //   cv_k_ck.hip    missing signers (cv_ck.h): one lane per transaction, one wave per large transaction
 //   cv_k_notary.hip the notary's fused commit step (cv_notary.h): gate, state-key gather, finalise + list, scatter
+//   cv_k_tearoff.hip the tear-off verifier and the oracle's signing step (cv_tearoff.h): check bytes, gate, compaction
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #include "cv_uniq.h"
 #include "cv_ck.h"
 #include "cv_notary.h"
+#include "cv_tearoff.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -188,6 +190,10 @@ __global__ void cv_notary_gate_kernel(CvNotary N);
 __global__ void cv_notary_gather_kernel(CvNotary N);
 __global__ void cv_notary_final_kernel(CvNotary N, uint32_t *count);
 __global__ void cv_notary_scatter_kernel(uint32_t count, const uint32_t *list, const uint4 *sig, uint4 *out);
+// the tear-off verifier and the oracle's signing step (cv_k_tearoff.hip, cv_tearoff.h): the compaction is ONE workgroup
+__global__ void cv_tearoff_check_kernel(CvTearoff T);
+__global__ void cv_tearoff_gate_kernel(CvTearoff T);
+__global__ void cv_tearoff_compact_kernel(CvTearoff T, uint32_t *count);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

@@ -447,6 +447,25 @@ hipError_t cvk_notary_scatter(uint32_t count, const uint32_t *list, const uint8_
     return hipGetLastError();
 }
 
+hipError_t cvk_tearoff_check(const CvTearoff *T, hipStream_t stream) {
+    if (!T) return hipErrorInvalidValue;
+    if (T->nleaves == 0) return hipSuccess;
+    hipLaunchKernelGGL(cv_tearoff_check_kernel, uniq_grid(T->nleaves), dim3(CV_BLOCK), 0, stream, *T);
+    return hipGetLastError();
+}
+
+hipError_t cvk_tearoff_gate(const CvTearoff *T, hipStream_t stream) {
+    if (!T || T->ntx == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_tearoff_gate_kernel, uniq_grid(T->ntx), dim3(CV_BLOCK), 0, stream, *T);
+    return hipGetLastError();
+}
+
+hipError_t cvk_tearoff_compact(const CvTearoff *T, uint32_t *count, hipStream_t stream) {
+    if (!T || T->ntx == 0 || !count) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_tearoff_compact_kernel, dim3(1), dim3(CVT_SCAN_BLOCK), 0, stream, *T, count);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

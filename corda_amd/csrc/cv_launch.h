@@ -6,6 +6,7 @@
 
 #include "cv_ck.h"
 #include "cv_notary.h"
+#include "cv_tearoff.h"
 #include "cv_uniq.h"
 
 // Helper stream and events of one verify workspace slot, used by cvk_verify's drain overlap (a
@@ -108,6 +109,14 @@ hipError_t cvk_notary_gate(const CvNotary *N, hipStream_t stream);
 hipError_t cvk_notary_gather(const CvNotary *N, hipStream_t stream);
 hipError_t cvk_notary_final(const CvNotary *N, uint32_t *count, hipStream_t stream);
 hipError_t cvk_notary_scatter(uint32_t count, const uint32_t *list, const uint8_t *sig, uint8_t *out, hipStream_t stream);
+// The tear-off verifier and the oracle's signing step (cv_tearoff.h; kernels in cv_k_tearoff.hip), every step enqueued
+// on `stream`, nothing synchronised.  check: one lane per filtered leaf -> the check bytes (after the leaf kernel:
+// cvk_merkle with ntx == 0; nleaves == 0 launches nothing).  gate: one lane per tear-off -> outcome, first_bad and,
+// where asked for, fv_verdict / fv_status (after cvk_pmt_verify).  compact: ONE workgroup -> the ascending list of
+// accepted tear-offs with their signing records, its length in *count (then cvk_sign_keyed and cvk_notary_scatter).
+hipError_t cvk_tearoff_check(const CvTearoff *T, hipStream_t stream);
+hipError_t cvk_tearoff_gate(const CvTearoff *T, hipStream_t stream);
+hipError_t cvk_tearoff_compact(const CvTearoff *T, uint32_t *count, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

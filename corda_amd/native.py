@@ -24,7 +24,9 @@ CV_TX_OK = 0
 CV_TX_EMPTY = 1
 CV_PMT_OK = 0
 CV_PMT_EMPTY = 1
+CV_PMT_MALFORMED = 2
 CV_PMT_NOT_IN_TREE = 3
+CV_PMT_NO_INCLUDED = 4
 CV_UNIQ_OK = 0
 CV_UNIQ_CONFLICT = 1
 CV_UNIQ_SKIPPED = 2
@@ -37,6 +39,11 @@ CV_VS_MALFORMED = 3
 # cv_notarise_batch outcome[t] (CV_NS_*)
 CV_NS_SUCCESS, CV_NS_EMPTY, CV_NS_ID_MISMATCH, CV_NS_TIMESTAMP_INVALID, CV_NS_TX_INVALID = 0, 1, 2, 3, 4
 CV_NS_BAD_KEY, CV_NS_SIGNATURES_MISSING, CV_NS_MALFORMED, CV_NS_CONFLICT = 5, 6, 7, 8
+# cv_tearoff_sign_batch outcome[t] (CV_TS_*), its leaf_pre codes and first_bad's "no leaf"
+CV_TS_SUCCESS, CV_TS_NO_LEAVES, CV_TS_MALFORMED, CV_TS_VERIFY_FAILED = 0, 1, 2, 3
+CV_TS_NOT_COMMANDS, CV_TS_WRONG_COMMAND, CV_TS_UNKNOWN = 4, 5, 6
+TS_PRE_OK, TS_PRE_NOT_COMMAND, TS_PRE_WRONG_COMMAND, TS_PRE_UNKNOWN = 0, 1, 2, 3
+TS_NO_LEAF = 0xFFFFFFFF
 NS_NO_SIG = 0xFFFFFFFF            # first_bad: no signature of the transaction settled its outcome
 NS_PRE_SIGNATURE, NS_PRE_KEY = 1, 2   # sig_pre: the host prefilter's SignatureException / InvalidKeyException
 CK_WIDE_DEFAULT, CK_WIDE_ALWAYS, CK_WIDE_NEVER = 0, 1, 0xFFFFFFFF      # cv_missing_signers' wide_min
@@ -58,7 +65,7 @@ EXPORTED = (
     "cv_uniq_open", "cv_uniq_close", "cv_uniq_reserve", "cv_uniq_commit_batch", "cv_uniq_lookup", "cv_uniq_load",
     "cv_uniq_set_max_rounds", "cv_uniq_stats",
     "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
-    "cv_notarise_batch",
+    "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -204,6 +211,10 @@ def load():
         lib.cv_notarise_batch.argtypes = ([_vp, _vp, _vp, ctypes.c_int, _sz, _vp, ctypes.c_uint64] + [_vp] * 11 + [_sz] * 3 +
                                           [_vp] * 19)
         lib.cv_notarise_batch.restype = ctypes.c_int
+        lib.cv_filtered_verify.argtypes = [_vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp, _sz] + [_vp] * 8
+        lib.cv_filtered_verify.restype = ctypes.c_int
+        lib.cv_tearoff_sign_batch.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp, _sz] + [_vp] * 10
+        lib.cv_tearoff_sign_batch.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp]
         lib.cv_ed25519_sign_keyed.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed_device.argtypes = [_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -753,6 +764,67 @@ class Engine:
         _check(rc, "cv_notarise_batch")
         cut = {"outcome": ntx, "ids": ntx, "notary_sig": ntx, "first_bad": ntx, "req_missing": nreq}
         return {k: None if a is None else a[:cut.get(k, ns)] for k, a in zip(self.NOTARISE_OUTPUTS, o)}
+
+    def _tearoff_args(self, arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash, tree_begin, root):
+        """The shared inputs of filtered_verify and tearoff_sign_batch as the library takes them."""
+        ntx, arena, leaf_off, leaf_len, tx_leaf_begin = self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
+        tree_begin = np.ascontiguousarray(tree_begin, dtype=np.uint32)
+        if ntx < 0 or tree_begin.shape[0] != ntx + 1:
+            raise ValueError("tx_leaf_begin and tree_begin must have ntx + 1 entries")
+        nnodes = int(tree_begin[-1]) if ntx else 0
+
+        def arr(a, dt, n, what, width=1):
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.size < n * width:
+                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
+            return a if a.size else np.zeros(width, dt)
+        nodes = [arr(kind, np.uint8, nnodes, "kind"), arr(left, np.uint32, nnodes, "left"),
+                 arr(right, np.uint32, nnodes, "right"), arr(node_hash, np.uint8, nnodes, "node_hash", 32)]
+        root = arr(root, np.uint8, ntx, "root", 32)
+        return ntx, nnodes, (arena, leaf_off, leaf_len, tx_leaf_begin), nodes, tree_begin, root
+
+    def filtered_verify(self, arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash, tree_begin, root
+                        ) -> Tuple[np.ndarray, np.ndarray]:
+        """cv_filtered_verify: FilteredTransaction.verify for every tear-off from its FILTERED leaves' blobs (as
+        merkle_tx_ids takes them, cut by tx_leaf_begin) and the flat trees of partial_merkle_verify / filtered_build
+        -> (verdict[ntx], status[ntx]); status CV_PMT_NO_INCLUDED for a tear-off without filtered leaves."""
+        ntx, nnodes, (arena, leaf_off, leaf_len, txb), nodes, tree_begin, root = self._tearoff_args(
+            arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash, tree_begin, root)
+        verdict, status = np.zeros(max(ntx, 1), np.uint8), np.zeros(max(ntx, 1), np.uint8)
+        rc = self._lib.cv_filtered_verify(self._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len), _p(txb), nnodes,
+                                          *[_p(a) for a in nodes], _p(tree_begin), _p(root), _p(verdict), _p(status))
+        if rc == -3:
+            self._merkle_args(arena, leaf_off, leaf_len, txb, scan=True)   # leaves past the arena: ValueError
+        _check(rc, "cv_filtered_verify")
+        return verdict[:ntx], status[:ntx]
+
+    def tearoff_sign_batch(self, signer: "Signer", arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash,
+                           tree_begin, root, leaf_pre=None, out=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """cv_tearoff_sign_batch: NodeInterestRates.Oracle.sign for every tear-off in one call — the inputs of
+        filtered_verify, leaf_pre u8[nleaves] or None (TS_PRE_*: the service's verdict on each filtered leaf) ->
+        (outcome u8[ntx] CV_TS_*, first_bad u32[ntx], sig (ntx,64) u8: the signer's signature over the root of an
+        accepted tear-off, zero bytes for a refused one).  out: (outcome, first_bad or None, sig) to write into."""
+        ntx, nnodes, (arena, leaf_off, leaf_len, txb), nodes, tree_begin, root = self._tearoff_args(
+            arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash, tree_begin, root)
+        nl = int(txb[-1]) if ntx else 0
+        if leaf_pre is not None:
+            leaf_pre = np.ascontiguousarray(leaf_pre, dtype=np.uint8).reshape(-1)
+            if leaf_pre.size < nl:
+                raise ValueError("leaf_pre must have one entry per filtered leaf")
+            if leaf_pre.size == 0:
+                leaf_pre = np.zeros(1, np.uint8)
+        q = max(ntx, 1)
+        outcome, first_bad, sig = out if out is not None else (np.zeros(q, np.uint8), np.zeros(q, np.uint32),
+                                                               np.zeros((q, 64), np.uint8))
+        if not signer._h:
+            raise ValueError("the signer is closed")
+        rc = self._lib.cv_tearoff_sign_batch(self._h, signer._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len),
+                                             _p(txb), nnodes, *[_p(a) for a in nodes], _p(tree_begin), _p(root),
+                                             _p(leaf_pre), _p(outcome), _p(first_bad), _p(sig))
+        if rc == -3:
+            self._merkle_args(arena, leaf_off, leaf_len, txb, scan=True)   # leaves past the arena: ValueError
+        _check(rc, "cv_tearoff_sign_batch")
+        return outcome[:ntx], None if first_bad is None else first_bad[:ntx], sig[:ntx]
 
     # ------------------------------------------------------------ device-resident API
     def missing_signers_device(self, device: int, ntx: int, nreq: int, nnodes: int, nchild: int, nsig: int, d_kind: int,

@@ -647,6 +647,58 @@ def verify_filtered_batch(items, engine: Optional[native.Engine] = None) -> List
     return verify_partial_trees(batch, engine)
 
 
+def flatten_filtered(items, classify=None):
+    """The arrays of Engine.filtered_verify / Engine.tearoff_sign_batch for items (ftx, root): the filtered leaves'
+    blobs in getFilteredHashes order (inputs, outputs, attachments, commands), the flat trees, the roots — and, with
+    classify(group, leaf_bytes) -> 0..3, leaf_pre.  -> (arena, off, len, tx_leaf_begin, kind, left, right, node_hash,
+    tree_begin, root, leaf_pre or None)."""
+    leaves: List[bytes] = []
+    pre: List[int] = []
+    kind: List[int] = []
+    left: List[int] = []
+    right: List[int] = []
+    hashes: List[bytes] = []
+    lb, tb = [0], [0]
+    roots: List[bytes] = []
+    for ftx, root in items:
+        fl = ftx.filtered_leaves
+        for group, blobs in (("inputs", fl.inputs), ("outputs", fl.outputs), ("attachments", fl.attachments),
+                             ("commands", fl.commands)):
+            leaves.extend(blobs)
+            if classify is not None:
+                pre.extend(int(classify(group, b)) for b in blobs)
+        lb.append(len(leaves))
+        k, l, r, h = ftx.partial_merkle_tree.flatten(len(kind))
+        kind += k; left += l; right += r; hashes += h
+        tb.append(len(kind))
+        roots.append(root.bytes)
+    lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
+    offs = np.zeros(len(leaves), np.uint64)
+    if len(leaves) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+    return (arena, offs, lens, np.array(lb, np.uint32), np.array(kind, np.uint8), np.array(left, np.uint32),
+            np.array(right, np.uint32), np.frombuffer(b"".join(hashes), np.uint8).reshape(-1, 32),
+            np.array(tb, np.uint32), np.frombuffer(b"".join(roots), np.uint8).reshape(-1, 32),
+            np.array(pre, np.uint8) if classify is not None else None)
+
+
+def verify_filtered_batch_fused(items, engine: Optional[native.Engine] = None) -> List[bool]:
+    """verify_filtered_batch with the filtered hashes made on the GPU: FilteredTransaction.verify(root) for many
+    tear-offs in ONE cv_filtered_verify call from the leaves' bytes (no host hashing).  items: (ftx, root).  The first
+    tear-off without leaves raises the reference's MerkleTreeException, as the sequential loop would."""
+    if not items:
+        return []
+    eng = engine or native.default_engine()
+    v, st = eng.filtered_verify(*flatten_filtered(items)[:10])
+    for t in range(len(items)):
+        if st[t] == native.CV_PMT_NO_INCLUDED:
+            raise MerkleTreeException("Transaction without included leaves.")
+        if st[t] != native.CV_PMT_OK:
+            raise IllegalArgumentException("malformed partial Merkle tree encoding")
+    return [bool(x) for x in v]
+
+
 def build_filtered_batch(wtxs: Sequence[WireTransaction], filters, engine: Optional[native.Engine] = None,
                          raise_first: bool = True):
     """FilteredTransaction.buildMerkleTransaction for many transactions in ONE GPU call (cv_filtered_build: leaf

@@ -38,6 +38,13 @@
  *                                 PartialMerkleTree.kt:69-111 over MerkleTree.getMerkleTree (MerkleTransaction.kt:66-99)
  *   cv_filtered_build         N x  FilteredTransaction.buildMerkleTransaction (MerkleTransaction.kt:146-168): leaf
  *                                 hashes, full tree and pruned tree of every tear-off in one call
+ *   cv_filtered_verify        N x  FilteredTransaction.verify(merkleRoot) from the filtered leaves' bytes
+ *                                 MerkleTransaction.kt:112-117,173-178 with PartialMerkleTree.kt:118-144: the
+ *                                 filtered hashes are made on the device
+ *   cv_tearoff_sign_batch     N x  NodeInterestRates.Oracle.sign(ftx, merkleRoot)
+ *                                 samples/irs-demo/src/main/kotlin/net/corda/irs/api/NodeInterestRates.kt:190-225
+ *                                 (client: RatesFixFlow.kt:100-110): the tear-off verified, the oracle's refusals in
+ *                                 the reference's order and the root signed with its fixed key, in one call
  *   cv_uniq_open +            N x  UniquenessProvider.commit(states, txId, callerIdentity)
  *   cv_uniq_commit_batch          core/src/main/kotlin/net/corda/core/node/services/UniquenessProvider.kt:13-35 as
  *                                 InMemoryUniquenessProvider.kt:14-36 decides it (the decision half of
@@ -566,6 +573,65 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *s, int validatin
     uint8_t *req_missing /* nreq, optional */, uint8_t *state_conflict /* nstates */,
     uint8_t *consumed_id /* nstates*32 */, uint32_t *consumed_index /* nstates */,
     uint32_t *consumed_caller /* nstates */);
+
+/* N x FilteredTransaction.verify(merkleRoot) (MerkleTransaction.kt:173-178 with PartialMerkleTree.kt:118-144) from
+ * the tear-offs' leaf BLOBS: the verifier's counterpart of cv_filtered_build.  The check list of tree t —
+ * FilteredLeaves.getFilteredHashes(), MerkleTransaction.kt:112-117 — is the SHA-256 digests of its filtered leaves,
+ * computed on the device by the leaf kernel of cv_merkle_tx_ids; they are never uploaded and never hashed on the host.
+ *   - verdict[t] and status[t] (optional) are cv_partial_merkle_verify's over those digests, result for result.
+ *   - A tear-off with no filtered leaves gets verdict 0 and status CV_PMT_NO_INCLUDED: the reference tests
+ *     `hashes.size == 0` (:175-176) before it touches the tree, so this wins over CV_PMT_MALFORMED.
+ * Synchronous, on one device (the least loaded).  All before any device work: the ranges as
+ * cv_partial_merkle_verify's for tree_begin and the same rules for tx_leaf_begin (begin[0] == 0, monotone, the end
+ * equals the count: CV_E_ARGS otherwise); a leaf past leaf_arena[leaf_arena_bytes), or whose off + len wraps, is
+ * CV_E_ARGS; more than 0xfffffffe tear-offs, leaves or nodes CV_E_TOO_LARGE; ntx == 0 returns CV_OK and touches
+ * nothing; a NULL context is checked last. */
+#define CV_PMT_NO_INCLUDED 4   /* MerkleTreeException("Transaction without included leaves.") */
+int cv_filtered_verify(cv_ctx *ctx, size_t ntx,
+    /* the FILTERED leaves of tear-off t, serialised, in getFilteredHashes order (inputs, outputs, attachments,
+       commands): blobs as cv_merkle_tx_ids_bounded takes them */
+    const uint8_t *leaf_arena, uint64_t leaf_arena_bytes, const uint64_t *leaf_off, const uint32_t *leaf_len,
+    const uint32_t *tx_leaf_begin /* ntx+1 */,
+    /* the partial trees, exactly the arrays of cv_partial_merkle_verify / the outputs of cv_filtered_build */
+    size_t nnodes, const uint8_t *kind, const uint32_t *left, const uint32_t *right,
+    const uint8_t *node_hash /* nnodes*32 */, const uint32_t *tree_begin /* ntx+1 */,
+    const uint8_t *root /* ntx*32 */, uint8_t *verdict /* ntx */, uint8_t *status /* ntx, optional */);
+
+/* N x NodeInterestRates.Oracle.sign(ftx, merkleRoot) (samples/irs-demo/src/main/kotlin/net/corda/irs/api/
+ * NodeInterestRates.kt:190-225; the client is RatesFixFlow.kt:100-110) in one call: the tear-off verified as
+ * cv_filtered_verify does, the oracle's refusals in the reference's order, the root signed with the service's fixed
+ * key.  The binding decodes the leaves (Kryo stays on the JVM) and passes one byte per filtered leaf, leaf_pre:
+ *   0 fine; 1 not a command — an input, output or attachment (the require at :197); 2 a command the service does not
+ *   vouch for — not a Fix, or the oracle is not among its signers (:199-205); 3 a command it vouches for whose data
+ *   it does not know, or knows differently (UnknownFix, :213-217).  Any other value: CV_E_ARGS before any device work.
+ * outcome[t], first match wins:
+ *   CV_TS_NO_LEAVES, CV_TS_MALFORMED, CV_TS_VERIFY_FAILED from the verify (its status CV_PMT_NO_INCLUDED,
+ *   CV_PMT_MALFORMED, its verdict 0); then CV_TS_NOT_COMMANDS, CV_TS_WRONG_COMMAND, CV_TS_UNKNOWN for the LOWEST class
+ *   of leaf_pre present among the tear-off's leaves — each of the reference's tests looks at every leaf before the
+ *   next one runs; CV_TS_SUCCESS otherwise.  The reference's `fixes.isEmpty()` branch (:208-209) cannot be reached:
+ *   past the first tests there is at least one leaf and every leaf is a command the service vouches for.
+ * first_bad[t] (optional): for CV_TS_NOT_COMMANDS / WRONG_COMMAND / UNKNOWN the absolute index of the first filtered
+ *   leaf of the deciding class (the reference names the first unknown fix in order); 0xffffffff for every other outcome.
+ * sig_out[t] = cv_ed25519_sign_keyed(s) over the 32 bytes of root[t] when outcome[t] == CV_TS_SUCCESS, bit for bit —
+ *   signingKey.signWithECDSA(merkleRoot.bytes, identity), :224 — and 64 zero bytes otherwise.  The signing kernel
+ *   runs for the accepted tear-offs alone: a signature over a refused root reaches no host-visible buffer.
+ * s must belong to ctx.  Synchronous, on one device (the least loaded); one upload, two synchronisations (the
+ * accepted count, the read-back).  Argument checks as cv_filtered_verify. */
+#define CV_TS_SUCCESS        0  /* sig_out[t] = signature over root[t]                                        */
+#define CV_TS_NO_LEAVES      1  /* MerkleTreeException out of ftx.verify (MerkleTransaction.kt:175-176)       */
+#define CV_TS_MALFORMED      2  /* the nodes are not a tree encoding: the shim throws IllegalArgumentException */
+#define CV_TS_VERIFY_FAILED  3  /* MerkleTreeException("... Couldn't verify partial Merkle tree.") (:191-193) */
+#define CV_TS_NOT_COMMANDS   4  /* some leaf_pre == 1: IllegalArgumentException (the require at :197)         */
+#define CV_TS_WRONG_COMMAND  5  /* some leaf_pre == 2: IllegalArgumentException (:204-205)                    */
+#define CV_TS_UNKNOWN        6  /* some leaf_pre == 3: UnknownFix of leaf first_bad[t] (:213-217)             */
+int cv_tearoff_sign_batch(cv_ctx *ctx, const cv_signer *s, size_t ntx,
+    /* the filtered leaves and the partial trees: the inputs of cv_filtered_verify */
+    const uint8_t *leaf_arena, uint64_t leaf_arena_bytes, const uint64_t *leaf_off, const uint32_t *leaf_len,
+    const uint32_t *tx_leaf_begin /* ntx+1 */, size_t nnodes, const uint8_t *kind, const uint32_t *left,
+    const uint32_t *right, const uint8_t *node_hash /* nnodes*32 */, const uint32_t *tree_begin /* ntx+1 */,
+    const uint8_t *root /* ntx*32 */,
+    const uint8_t *leaf_pre /* nleaves, NULL = none: the service's verdict on each filtered leaf's CONTENT */,
+    uint8_t *outcome /* ntx */, uint32_t *first_bad /* ntx, optional */, uint8_t *sig_out /* ntx*64 */);
 
 /* ---------------------------------------------------------------- device-resident API
  * All pointers are device pointers on HIP device `device` (which must be in the context); work is
