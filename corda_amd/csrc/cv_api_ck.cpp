@@ -1,20 +1,13 @@
 // cv_api_ck.cpp — missing signers of the C-ABI (include/cordaverify.h): cv_missing_signers, its device-resident form
-// and the workspace size.  The per-lane logic is cv_ck.h's; the engine state is cv_host.h's.
-#include "cv_host.h"
+// and the workspace size.  The per-lane logic is cv_ck.h's; the engine state is cv_host.h's; the range checks, the
+// buffer's layout and CvCk over it are cv_batch.h's.
+#include "cv_batch.h"
 
 using namespace cvh;
 
 static_assert(CV_VS_OK == CVCK_VS_OK && CV_VS_BAD_SIGNATURE == CVCK_VS_BAD_SIGNATURE && CV_VS_MISSING == CVCK_VS_MISSING &&
                   CV_VS_MALFORMED == CVCK_VS_MALFORMED && CV_CK_LEAF == 0 && CV_CK_NODE == 1,
               "cv_ck.h and the public header agree");
-
-// begin[0] == 0, monotone, begin[n] == total
-static bool ranges_ok(const uint32_t *begin, size_t n, size_t total) {
-    if (begin[0] != 0 || begin[n] != total) return false;
-    for (size_t i = 0; i < n; i++)
-        if (begin[i + 1] < begin[i]) return false;
-    return true;
-}
 
 extern "C" {
 
@@ -39,22 +32,17 @@ int cv_missing_signers(cv_ctx *ctx, size_t ntx, size_t nreq, size_t nnodes, size
         return CV_E_ARGS;
     if (nnodes ? (child_begin[0] != 0 || child_begin[nnodes] != nchild) : nchild != 0) return CV_E_ARGS;
     if (!ctx) return CV_E_ARGS;
-    Opts o = ctx->opts();
-    o.shard_min = o.spread_min = SIZE_MAX;   // one device, the least loaded
-    return dispatch(ctx, o, ntx, 1, [&](Device &d, size_t, size_t, int) {
+    return dispatch_one(ctx, ntx, [&](Device &d, size_t, size_t, int) {
         CV_TRY(hipSetDevice(d.ordinal));
         const size_t nwords = (nsig + 63) / 64;
-        const size_t o_kind = 0, o_key = al16(o_kind + nnodes), o_thr = al16(o_key + 32 * nnodes);
-        const size_t o_cb = al16(o_thr + 4 * nnodes), o_child = al16(o_cb + 4 * (nnodes + 1));
-        const size_t o_w = al16(o_child + 4 * nchild), o_rb = al16(o_w + 4 * nchild), o_trb = al16(o_rb + 4 * (nreq + 1));
-        const size_t o_sig = al16(o_trb + 4 * (ntx + 1)), o_tsb = al16(o_sig + 32 * nsig);
-        const size_t o_allow = al16(o_tsb + 4 * (ntx + 1)), o_bm = al16(o_allow + nreq), o_miss = al16(o_bm + 8 * nwords);
-        const size_t o_st = al16(o_miss + nreq), o_ws = al16(o_st + ntx);
-        const size_t total = o_ws + (size_t)cvck_ws_bytes(ntx, nnodes);
-        CV_TRY(d.ck.ensure(total));
+        Layout lay;
+        const size_t o_kind = lay.take(nnodes), o_key = lay.take(32 * nnodes), o_thr = lay.take(4 * nnodes);
+        const size_t o_cb = lay.take(4 * (nnodes + 1)), o_child = lay.take(4 * nchild), o_w = lay.take(4 * nchild);
+        const size_t o_rb = lay.take(4 * (nreq + 1)), o_trb = lay.take(4 * (ntx + 1)), o_sig = lay.take(32 * nsig);
+        const size_t o_tsb = lay.take(4 * (ntx + 1)), o_allow = lay.take(nreq), o_bm = lay.take(8 * nwords);
+        const size_t o_miss = lay.take(nreq), o_st = lay.take(ntx), o_ws = lay.take((size_t)cvck_ws_bytes(ntx, nnodes));
+        CV_TRY(d.ck.ensure(lay.top));
         uint8_t *base = d.ck.as<uint8_t>();
-        auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
-        auto i32 = [base](size_t off) { return reinterpret_cast<int32_t *>(base + off); };
         hipStream_t s = d.stream;
         auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
         auto up = [&](size_t off, const void *src, size_t bytes) {
@@ -72,17 +60,10 @@ int cv_missing_signers(cv_ctx *ctx, size_t ntx, size_t nreq, size_t nnodes, size
         CV_TRY(up(o_tsb, tx_sig_begin, 4 * (ntx + 1)));
         if (req_allowed) CV_TRY(up(o_allow, req_allowed, nreq));
         if (verdict_bitmap) CV_TRY(up(o_bm, verdict_bitmap, 8 * nwords));
-        CvCk a{};
-        a.ntx = (uint32_t)ntx, a.nreq = (uint32_t)nreq, a.nnodes = (uint32_t)nnodes, a.nchild = (uint32_t)nchild;
-        a.nsig = (uint32_t)nsig;
-        a.kind = base + o_kind, a.leaf_key = base + o_key, a.threshold = i32(o_thr), a.child_begin = u32(o_cb);
-        a.child = u32(o_child), a.weight = i32(o_w), a.req_begin = u32(o_rb), a.tx_req_begin = u32(o_trb);
-        a.sig_key = base + o_sig, a.tx_sig_begin = u32(o_tsb);
-        a.req_allowed = req_allowed ? base + o_allow : nullptr;
-        a.bitmap = verdict_bitmap ? reinterpret_cast<const uint64_t *>(base + o_bm) : nullptr;
-        a.wide_min = wide_min;
-        a.count = u32(o_ws), a.list = u32(o_ws + CVCK_WS_LIST), a.flag = base + o_ws + cvck_ws_flag_off(ntx);
-        a.req_missing = base + o_miss, a.tx_status = base + o_st;
+        const CvCk a = ck_args(base, {ntx, nreq, nnodes, nchild, nsig},
+                               {o_kind, o_key, o_thr, o_cb, o_child, o_w, o_rb, o_trb, o_sig, o_tsb, o_allow, o_bm, o_ws,
+                                o_miss, o_st},
+                               req_allowed != nullptr, verdict_bitmap != nullptr, wide_min);
         CV_TRY(cvk_ck(&a, s));
         if (nreq) CV_TRY(hipMemcpyAsync(req_missing, base + o_miss, nreq, hipMemcpyDeviceToHost, s));
         CV_TRY(hipMemcpyAsync(tx_status, base + o_st, ntx, hipMemcpyDeviceToHost, s));

@@ -1,6 +1,7 @@
 // cv_api_pmt.cpp — partial Merkle trees (tear-offs) of the C-ABI (include/cordaverify.h): cv_partial_merkle_verify
-// and the builds, cv_partial_merkle_build and cv_filtered_build.  The engine state is cv_host.h's.
-#include "cv_host.h"
+// and the builds, cv_partial_merkle_build and cv_filtered_build.  The engine state is cv_host.h's; the range checks,
+// the buffer's layout and the routing to one device are cv_batch.h's.
+#include "cv_batch.h"
 
 using namespace cvh;
 
@@ -17,22 +18,15 @@ int cv_partial_merkle_verify(cv_ctx *ctx, size_t ntrees, size_t nnodes, const ui
     if (ncheck && !check) return CV_E_ARGS;
     if (ntrees > 0xfffffffeull || nnodes > 0xfffffffeull || ncheck > 0xfffffffeull) return CV_E_TOO_LARGE;
     // the ranges must be well formed for the kernel to stay inside the buffers
-    if (tree_begin[0] != 0 || tree_begin[ntrees] != nnodes || check_begin[0] != 0 || check_begin[ntrees] != ncheck)
-        return CV_E_ARGS;
-    for (size_t t = 0; t < ntrees; t++)
-        if (tree_begin[t + 1] < tree_begin[t] || check_begin[t + 1] < check_begin[t]) return CV_E_ARGS;
-    Opts o = ctx->opts();
-    o.shard_min = o.spread_min = SIZE_MAX;   // one device, the least loaded (tear-off batches are small)
-    return dispatch(ctx, o, ntrees, 1, [&](Device &d, size_t, size_t, int) {
+    if (!ranges_ok(tree_begin, ntrees, nnodes) || !ranges_ok(check_begin, ntrees, ncheck)) return CV_E_ARGS;
+    return dispatch_one(ctx, ntrees, [&](Device &d, size_t, size_t, int) {   // tear-off batches are small
         CV_TRY(hipSetDevice(d.ordinal));
-        auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        const size_t o_kind = 0, o_left = up16(o_kind + nnodes), o_right = up16(o_left + 4 * nnodes);
-        const size_t o_hash = up16(o_right + 4 * nnodes), o_tb = up16(o_hash + 32 * nnodes);
-        const size_t o_root = up16(o_tb + 4 * (ntrees + 1)), o_check = up16(o_root + 32 * ntrees);
-        const size_t o_cb = up16(o_check + 32 * ncheck), o_verdict = up16(o_cb + 4 * (ntrees + 1));
-        const size_t o_status = up16(o_verdict + ntrees), o_dig = up16(o_status + ntrees);
-        const size_t o_flag = up16(o_dig + 32 * nnodes), total = up16(o_flag + nnodes + 1);
-        CV_TRY(d.pmt.ensure(total));
+        Layout lay;
+        const size_t o_kind = lay.take(nnodes), o_left = lay.take(4 * nnodes), o_right = lay.take(4 * nnodes);
+        const size_t o_hash = lay.take(32 * nnodes), o_tb = lay.take(4 * (ntrees + 1)), o_root = lay.take(32 * ntrees);
+        const size_t o_check = lay.take(32 * ncheck), o_cb = lay.take(4 * (ntrees + 1)), o_verdict = lay.take(ntrees);
+        const size_t o_status = lay.take(ntrees), o_dig = lay.take(32 * nnodes), o_flag = lay.take(nnodes + 1);
+        CV_TRY(d.pmt.ensure(lay.top));
         uint8_t *base = d.pmt.as<uint8_t>();
         hipStream_t s = d.stream;
         auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
@@ -46,11 +40,10 @@ int cv_partial_merkle_verify(cv_ctx *ctx, size_t ntrees, size_t nnodes, const ui
         CV_TRY(hipMemcpyAsync(base + o_root, root, 32 * ntrees, hipMemcpyHostToDevice, s));
         if (ncheck) CV_TRY(hipMemcpyAsync(base + o_check, check, 32 * ncheck, hipMemcpyHostToDevice, s));
         CV_TRY(hipMemcpyAsync(base + o_cb, check_begin, 4 * (ntrees + 1), hipMemcpyHostToDevice, s));
-        CV_TRY(cvk_pmt_verify((uint32_t)ntrees, base + o_kind, reinterpret_cast<uint32_t *>(base + o_left),
-                              reinterpret_cast<uint32_t *>(base + o_right), base + o_hash,
-                              reinterpret_cast<uint32_t *>(base + o_tb), base + o_root, base + o_check,
-                              reinterpret_cast<uint32_t *>(base + o_cb), reinterpret_cast<uint32_t *>(base + o_dig),
-                              base + o_flag, base + o_verdict, base + o_status, s));
+        CV_TRY(cvk_pmt_verify((uint32_t)ntrees, base + o_kind, at<uint32_t>(base, o_left), at<uint32_t>(base, o_right),
+                              base + o_hash, at<uint32_t>(base, o_tb), base + o_root, base + o_check,
+                              at<uint32_t>(base, o_cb), at<uint32_t>(base, o_dig), base + o_flag, base + o_verdict,
+                              base + o_status, s));
         CV_TRY(hipMemcpyAsync(verdict, base + o_verdict, ntrees, hipMemcpyDeviceToHost, s));
         if (status) CV_TRY(hipMemcpyAsync(status, base + o_status, ntrees, hipMemcpyDeviceToHost, s));
         CV_TRY(hipStreamSynchronize(s));
@@ -117,16 +110,12 @@ static int pmtb_check(cv_ctx *ctx, const PmtbIn &in, const PmtbOut &out, std::ve
     if (in.ntx > 0xfffffffeull) return CV_E_TOO_LARGE;
     if (!in.txb || !out.tree_begin || !out.status || !out.nnodes) return CV_E_ARGS;
     if (out.cap && (!out.kind || !out.left || !out.right || !out.node_hash)) return CV_E_ARGS;
-    if (in.txb[0] != 0) return CV_E_ARGS;
-    for (size_t t = 0; t < in.ntx; t++)
-        if (in.txb[t + 1] < in.txb[t]) return CV_E_ARGS;
+    if (!ranges_ok(in.txb, in.ntx)) return CV_E_ARGS;
     const size_t nl = in.txb[in.ntx];
     if (in.keep ? (nl && (!in.off || !in.len)) : (nl && !in.leaf_hash)) return CV_E_ARGS;
     size_t ninc = 0;
     if (!in.keep) {
-        if (!in.inc_begin || in.inc_begin[0] != 0) return CV_E_ARGS;
-        for (size_t t = 0; t < in.ntx; t++)
-            if (in.inc_begin[t + 1] < in.inc_begin[t]) return CV_E_ARGS;
+        if (!in.inc_begin || !ranges_ok(in.inc_begin, in.ntx)) return CV_E_ARGS;
         ninc = in.inc_begin[in.ntx];
         if (ninc && !in.include) return CV_E_ARGS;
     }
@@ -153,9 +142,7 @@ static int pmtb_check(cv_ctx *ctx, const PmtbIn &in, const PmtbOut &out, std::ve
 // Two synchronisations: tree_begin, ids and status come back first, then — the total known and within nodes_cap —
 // the node arrays' used part.
 static int pmtb_run(cv_ctx *ctx, const PmtbIn &in, const PmtbOut &out, const std::vector<uint32_t> &ws_off, uint64_t bound) {
-    Opts o = ctx->opts();
-    o.shard_min = o.spread_min = SIZE_MAX;
-    return dispatch(ctx, o, in.ntx, 1, [&](Device &d, size_t, size_t, int threads) {
+    return dispatch_one(ctx, in.ntx, [&](Device &d, size_t, size_t, int threads) {
         CV_TRY(hipSetDevice(d.ordinal));
         const size_t ntx = in.ntx, nl = in.txb[ntx], ninc = in.keep ? 0 : in.inc_begin[ntx];
         const size_t P = ws_off[ntx], B = (size_t)bound;
@@ -166,17 +153,15 @@ static int pmtb_run(cv_ctx *ctx, const PmtbIn &in, const PmtbOut &out, const std
             st = mstage_plan(0, ntx, in.txb, in.off, in.len, pool);
             if (!mstage_in_bounds(st, in.arena_bytes)) return CV_E_ARGS;   // past the arena, or a leaf's off + len wraps
         }
-        const size_t o_in = 0, o_ldig = o_in + (in.keep ? al16(st.total) : al16(32 * nl));
-        const size_t o_txb = o_ldig + (in.keep ? al16(32 * nl + 32) : 0), o_inc = o_txb + al16(4 * (ntx + 1));
-        const size_t o_ib = o_inc + al16(32 * ninc), o_keep = o_ib + al16(4 * (ntx + 1));
-        const size_t o_wso = o_keep + (in.keep ? al16(nl) : 0), o_dig = o_wso + al16(4 * (ntx + 1));
-        const size_t o_flag = o_dig + al16(32 * P), o_size = o_flag + al16(P), o_pos = o_size + al16(4 * P);
-        const size_t o_cnt = o_pos + al16(4 * P), o_tb = o_cnt + al16(4 * ntx), o_ids = o_tb + al16(4 * (ntx + 1));
-        const size_t o_st = o_ids + al16(32 * ntx), o_kind = o_st + al16(ntx), o_left = o_kind + al16(B);
-        const size_t o_right = o_left + al16(4 * B), o_hash = o_right + al16(4 * B), total = o_hash + al16(32 * B) + 16;
-        CV_TRY(d.pmt.ensure(total));
+        Layout lay;
+        const size_t o_in = lay.take(in.keep ? st.total : 32 * nl), o_ldig = lay.take(in.keep ? 32 * nl + 32 : 0);
+        const size_t o_txb = lay.take(4 * (ntx + 1)), o_inc = lay.take(32 * ninc), o_ib = lay.take(4 * (ntx + 1));
+        const size_t o_keep = lay.take(in.keep ? nl : 0), o_wso = lay.take(4 * (ntx + 1)), o_dig = lay.take(32 * P);
+        const size_t o_flag = lay.take(P), o_size = lay.take(4 * P), o_pos = lay.take(4 * P), o_cnt = lay.take(4 * ntx);
+        const size_t o_tb = lay.take(4 * (ntx + 1)), o_ids = lay.take(32 * ntx), o_st = lay.take(ntx), o_kind = lay.take(B);
+        const size_t o_left = lay.take(4 * B), o_right = lay.take(4 * B), o_hash = lay.take(32 * B);
+        CV_TRY(d.pmt.ensure(lay.top + 16));
         uint8_t *base = d.pmt.as<uint8_t>();
-        auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
         hipStream_t s = d.stream;
         auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
         CvkPmtBuild a{};
@@ -191,11 +176,10 @@ static int pmtb_run(cv_ctx *ctx, const PmtbIn &in, const PmtbOut &out, const std
             }
             if (nl) CV_TRY(hipMemcpyAsync(base + o_keep, in.keep, nl, hipMemcpyHostToDevice, s));
             // the leaf kernel alone (no transactions: the tree sweep that follows keeps the levels)
-            CV_TRY(cvk_merkle(0, (uint32_t)nl, 0, dv + st.o_ar - st.lo, reinterpret_cast<const uint64_t *>(dv + st.o_off),
-                              reinterpret_cast<const uint32_t *>(dv + st.o_len),
-                              reinterpret_cast<const uint32_t *>(dv + st.o_txb), u32(o_ldig), nullptr, nullptr, s));
-            a.leaf_dig = u32(o_ldig);
-            a.tx_leaf_begin = reinterpret_cast<const uint32_t *>(dv + st.o_txb);
+            a.leaf_dig = at<uint32_t>(base, o_ldig);
+            a.tx_leaf_begin = at<uint32_t>(dv, st.o_txb);
+            CV_TRY(cvk_merkle(0, (uint32_t)nl, 0, dv + st.o_ar - st.lo, at<uint64_t>(dv, st.o_off),
+                              at<uint32_t>(dv, st.o_len), a.tx_leaf_begin, at<uint32_t>(base, o_ldig), nullptr, nullptr, s));
             a.keep = base + o_keep;
         } else {
             if (nl) CV_TRY(hipMemcpyAsync(base + o_in, in.leaf_hash, 32 * nl, hipMemcpyHostToDevice, s));
@@ -203,23 +187,23 @@ static int pmtb_run(cv_ctx *ctx, const PmtbIn &in, const PmtbOut &out, const std
             if (ninc) CV_TRY(hipMemcpyAsync(base + o_inc, in.include, 32 * ninc, hipMemcpyHostToDevice, s));
             CV_TRY(hipMemcpyAsync(base + o_ib, in.inc_begin, 4 * (ntx + 1), hipMemcpyHostToDevice, s));
             a.leaf_hash = base + o_in;
-            a.tx_leaf_begin = u32(o_txb);
+            a.tx_leaf_begin = at<uint32_t>(base, o_txb);
             a.include = base + o_inc;
-            a.include_begin = u32(o_ib);
+            a.include_begin = at<uint32_t>(base, o_ib);
         }
         CV_TRY(hipMemcpyAsync(base + o_wso, ws_off.data(), 4 * (ntx + 1), hipMemcpyHostToDevice, s));
-        a.ws_off = u32(o_wso);
-        a.dig = u32(o_dig);
+        a.ws_off = at<uint32_t>(base, o_wso);
+        a.dig = at<uint32_t>(base, o_dig);
         a.flag = base + o_flag;
-        a.size = u32(o_size);
-        a.pos = u32(o_pos);
-        a.count = u32(o_cnt);
+        a.size = at<uint32_t>(base, o_size);
+        a.pos = at<uint32_t>(base, o_pos);
+        a.count = at<uint32_t>(base, o_cnt);
         a.ids = base + o_ids;
         a.status = base + o_st;
-        a.tree_begin = u32(o_tb);
+        a.tree_begin = at<uint32_t>(base, o_tb);
         a.kind = base + o_kind;
-        a.left = u32(o_left);
-        a.right = u32(o_right);
+        a.left = at<uint32_t>(base, o_left);
+        a.right = at<uint32_t>(base, o_right);
         a.node_hash = base + o_hash;
         CV_TRY(cvk_pmt_build((uint32_t)ntx, &a, s));
         CV_TRY(hipMemcpyAsync(out.tree_begin, base + o_tb, 4 * (ntx + 1), hipMemcpyDeviceToHost, s));

@@ -1,7 +1,7 @@
 // cv_api_sign.cpp — signing entry points of the C-ABI (include/cordaverify.h): cv_ed25519_sign_batch (a seed per
 // message), the fixed-key signer (cv_signer_*, cv_ed25519_sign_keyed) and their device-resident forms.  The engine
-// state is cv_host.h's.
-#include "cv_host.h"
+// state is cv_host.h's; the signer's record for a device is cv_batch.h's.
+#include "cv_batch.h"
 
 using namespace cvh;
 
@@ -119,7 +119,7 @@ void cv_signer_close(cv_signer *s) {
 }
 
 // One shard on device d: staged like sign_shard, minus the seeds and public keys.
-static int sign_keyed_shard(Device &d, const void *rec, size_t b, size_t e, const uint8_t *arena, const uint64_t *off,
+static int sign_keyed_shard(Device &d, const uint32_t *rec, size_t b, size_t e, const uint8_t *arena, const uint64_t *off,
                             const uint32_t *len, uint8_t *sig) {
     const size_t n = e - b;
     if (n == 0) return CV_OK;
@@ -140,8 +140,8 @@ static int sign_keyed_shard(Device &d, const void *rec, size_t b, size_t e, cons
     if (hi > lo) CV_TRY(hipMemcpyAsync(d.arena.p, arena + lo, hi - lo, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(d.off.p, off + b, n * 8, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(d.len.p, len + b, n * 4, hipMemcpyHostToDevice, s));
-    CV_TRY(cvk_sign_keyed((uint32_t)n, static_cast<const uint32_t *>(rec), d.arena.as<uint8_t>() - lo,
-                          d.off.as<uint64_t>(), d.len.as<uint32_t>(), d.sig.as<uint8_t>(), s));
+    CV_TRY(cvk_sign_keyed((uint32_t)n, rec, d.arena.as<uint8_t>() - lo, d.off.as<uint64_t>(), d.len.as<uint32_t>(),
+                          d.sig.as<uint8_t>(), s));
     CV_TRY(hipMemcpyAsync(sig + b * 64, d.sig.p, n * 64, hipMemcpyDeviceToHost, s));
     CV_TRY(hipStreamSynchronize(s));
     drain.armed = false;
@@ -159,7 +159,7 @@ int cv_ed25519_sign_keyed(cv_ctx *ctx, const cv_signer *s, size_t n, const uint8
     if (extent > msg_arena_bytes || (extent && !msg_arena)) return CV_E_ARGS;
     const Opts o = ctx->opts();
     return dispatch(ctx, o, n, 64, [&](Device &d, size_t b, size_t e, int) {
-        return sign_keyed_shard(d, s->rec[dev_index(ctx, d)], b, e, msg_arena, msg_off, msg_len, sig_out);
+        return sign_keyed_shard(d, signer_rec(s, d), b, e, msg_arena, msg_off, msg_len, sig_out);
     });
 }
 
@@ -189,9 +189,9 @@ int cv_ed25519_sign_keyed_device(cv_ctx *ctx, int device, const cv_signer *sg, s
     std::lock_guard<std::mutex> g(d->mu);              // enqueue only
     CV_TRY(hipSetDevice(d->ordinal));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : d->stream;
-    CV_TRY(cvk_sign_keyed((uint32_t)n, static_cast<const uint32_t *>(sg->rec[dev_index(ctx, *d)]),
-                          static_cast<const uint8_t *>(d_arena), static_cast<const uint64_t *>(d_off),
-                          static_cast<const uint32_t *>(d_len), static_cast<uint8_t *>(d_sig), s));
+    CV_TRY(cvk_sign_keyed((uint32_t)n, signer_rec(sg, *d), static_cast<const uint8_t *>(d_arena),
+                          static_cast<const uint64_t *>(d_off), static_cast<const uint32_t *>(d_len),
+                          static_cast<uint8_t *>(d_sig), s));
     return CV_OK;
 }
 

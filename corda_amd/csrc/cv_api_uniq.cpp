@@ -1,7 +1,7 @@
 // cv_api_uniq.cpp — the device-resident uniqueness set of the C-ABI (include/cordaverify.h): the cv_uniq_* entry
 // points and the decision helpers cv_api_notary.cpp shares (cvh::uniq_*).  The engine state, struct cv_uniq included,
-// is cv_host.h's.
-#include "cv_host.h"
+// is cv_host.h's; the range check and the workspace's layout are cv_batch.h's.
+#include "cv_batch.h"
 
 using namespace cvh;
 
@@ -177,14 +177,6 @@ int cv_uniq_stats(cv_uniq *u, uint64_t *out, size_t nout) {
     return CV_OK;
 }
 
-// begin[0] == 0 and monotone
-static bool uniq_ranges_ok(size_t ntx, const uint32_t *begin) {
-    if (begin[0] != 0) return false;
-    for (size_t t = 0; t < ntx; t++)
-        if (begin[t + 1] < begin[t]) return false;
-    return true;
-}
-
 int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const uint32_t *tx_state_begin,
                          const uint8_t *tx_id, const uint32_t *caller, const uint8_t *tx_enable, uint8_t *tx_status,
                          uint8_t *state_conflict, uint8_t *consumed_id, uint32_t *consumed_index,
@@ -192,7 +184,7 @@ int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const
     if (ntx == 0) return CV_OK;
     if (ntx > 0xfffffffeull) return CV_E_TOO_LARGE;
     if (!tx_state_begin || !tx_id || !caller || !tx_status) return CV_E_ARGS;
-    if (!uniq_ranges_ok(ntx, tx_state_begin)) return CV_E_ARGS;
+    if (!ranges_ok(tx_state_begin, ntx)) return CV_E_ARGS;
     const size_t S = tx_state_begin[ntx];
     if (S > 0xfffffffeull) return CV_E_TOO_LARGE;
     if (S && (!state_key || !state_conflict || !consumed_id || !consumed_index || !consumed_caller)) return CV_E_ARGS;
@@ -203,15 +195,14 @@ int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const
     CV_TRY(hipSetDevice(u->ordinal));
     const size_t T = ntx, bs = (size_t)uniq_bmask(S) + 1;
     // inputs | workspace | outputs (tx_status | state_conflict | consumed id, index, caller: one copy-back region)
-    const size_t o_key = 0, o_beg = o_key + al16(32 * S), o_id = o_beg + al16(4 * (T + 1)), o_cal = o_id + al16(32 * T);
-    const size_t o_en = o_cal + al16(4 * T), o_bt = o_en + al16(T), o_rep = o_bt + al16(4 * bs), o_res = o_rep + al16(4 * S);
-    const size_t o_stx = o_res + al16(4 * S), o_own = o_stx + al16(4 * S), o_last = o_own + al16(4 * S);
-    const size_t o_s0 = o_last + al16(4 * S), o_s1 = o_s0 + al16(4 * T), o_ts = o_s1 + al16(4 * T);
-    const size_t o_sc = o_ts + al16(T), o_cid = o_sc + al16(S), o_cix = o_cid + al16(32 * S), o_cc = o_cix + al16(4 * S);
-    const size_t total = o_cc + al16(4 * S) + 16;
-    CV_TRY(u->ws.ensure(total));
+    Layout lay;
+    const size_t o_key = lay.take(32 * S), o_beg = lay.take(4 * (T + 1)), o_id = lay.take(32 * T), o_cal = lay.take(4 * T);
+    const size_t o_en = lay.take(T), o_bt = lay.take(4 * bs), o_rep = lay.take(4 * S), o_res = lay.take(4 * S);
+    const size_t o_stx = lay.take(4 * S), o_own = lay.take(4 * S), o_last = lay.take(4 * S), o_s0 = lay.take(4 * T);
+    const size_t o_s1 = lay.take(4 * T), o_ts = lay.take(T), o_sc = lay.take(S), o_cid = lay.take(32 * S);
+    const size_t o_cix = lay.take(4 * S), o_cc = lay.take(4 * S);
+    CV_TRY(u->ws.ensure(lay.top + 16));
     uint8_t *base = u->ws.as<uint8_t>();
-    auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
     hipStream_t s = u->stream;
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });   // the pageable copies read the caller's arrays
     if (S) CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * S, hipMemcpyHostToDevice, s));
@@ -219,32 +210,32 @@ int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const
     CV_TRY(hipMemcpyAsync(base + o_id, tx_id, 32 * T, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(base + o_cal, caller, 4 * T, hipMemcpyHostToDevice, s));
     if (tx_enable) CV_TRY(hipMemcpyAsync(base + o_en, tx_enable, T, hipMemcpyHostToDevice, s));
-    CV_TRY(hipMemsetAsync(base + o_cid, 0, o_cc + al16(4 * S) - o_cid, s));   // records of states without a conflict: zero
+    CV_TRY(hipMemsetAsync(base + o_cid, 0, lay.top - o_cid, s));   // records of states without a conflict: zero
     int rc = uniq_stat_begin(u);
     if (rc != CV_OK) return rc;
     CvUniqBatch B{};
     B.ntx = (uint32_t)T;
     B.nstates = (uint32_t)S;
-    B.key = u32(o_key);
-    B.begin = u32(o_beg);
-    B.id = u32(o_id);
-    B.caller = u32(o_cal);
+    B.key = at<uint32_t>(base, o_key);
+    B.begin = at<uint32_t>(base, o_beg);
+    B.id = at<uint32_t>(base, o_id);
+    B.caller = at<uint32_t>(base, o_cal);
     B.enable = tx_enable ? base + o_en : nullptr;
-    B.btab = u32(o_bt);
+    B.btab = at<uint32_t>(base, o_bt);
     B.bmask = (uint32_t)(bs - 1);
-    B.rep = u32(o_rep);
-    B.res = u32(o_res);
-    B.state_tx = u32(o_stx);
-    B.owner = u32(o_own);
-    B.last = u32(o_last);
+    B.rep = at<uint32_t>(base, o_rep);
+    B.res = at<uint32_t>(base, o_res);
+    B.state_tx = at<uint32_t>(base, o_stx);
+    B.owner = at<uint32_t>(base, o_own);
+    B.last = at<uint32_t>(base, o_last);
     B.tx_status = base + o_ts;
     B.state_conflict = base + o_sc;
-    B.cons_id = u32(o_cid);
-    B.cons_index = u32(o_cix);
-    B.cons_caller = u32(o_cc);
+    B.cons_id = at<uint32_t>(base, o_cid);
+    B.cons_index = at<uint32_t>(base, o_cix);
+    B.cons_caller = at<uint32_t>(base, o_cc);
     B.dstat = u->dstat.as<uint32_t>();
     uint64_t rounds = 0;
-    rc = uniq_decide(u, B, u32(o_s0), u32(o_s1), &rounds);
+    rc = uniq_decide(u, B, at<uint32_t>(base, o_s0), at<uint32_t>(base, o_s1), &rounds);
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(tx_status, base + o_ts, T, hipMemcpyDeviceToHost, s));
     if (S) {
@@ -270,19 +261,19 @@ int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key, uint8_t *foun
     if (!u) return CV_E_ARGS;
     std::lock_guard<std::mutex> g(u->mu);
     CV_TRY(hipSetDevice(u->ordinal));
-    const size_t o_key = 0, o_f = o_key + al16(32 * n), o_cid = o_f + al16(n), o_cix = o_cid + al16(32 * n);
-    const size_t o_cc = o_cix + al16(4 * n), total = o_cc + al16(4 * n) + 16;
-    CV_TRY(u->ws.ensure(total));
+    Layout lay;
+    const size_t o_key = lay.take(32 * n), o_f = lay.take(n), o_cid = lay.take(32 * n), o_cix = lay.take(4 * n);
+    const size_t o_cc = lay.take(4 * n);
+    CV_TRY(u->ws.ensure(lay.top + 16));
     uint8_t *base = u->ws.as<uint8_t>();
-    auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
     hipStream_t s = u->stream;
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
     CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * n, hipMemcpyHostToDevice, s));
-    CV_TRY(hipMemsetAsync(base + o_cid, 0, total - 16 - o_cid, s));            // absent keys: zero records
+    CV_TRY(hipMemsetAsync(base + o_cid, 0, lay.top - o_cid, s));   // absent keys: zero records
     int rc = uniq_stat_begin(u);
     if (rc != CV_OK) return rc;
-    CV_TRY(cvk_uniq_lookup(&u->T, (uint32_t)n, u32(o_key), base + o_f, u32(o_cid), u32(o_cix), u32(o_cc),
-                           u->dstat.as<uint32_t>(), s));
+    CV_TRY(cvk_uniq_lookup(&u->T, (uint32_t)n, at<uint32_t>(base, o_key), base + o_f, at<uint32_t>(base, o_cid),
+                           at<uint32_t>(base, o_cix), at<uint32_t>(base, o_cc), u->dstat.as<uint32_t>(), s));
     CV_TRY(hipMemcpyAsync(found, base + o_f, n, hipMemcpyDeviceToHost, s));
     CV_TRY(hipMemcpyAsync(consumed_id, base + o_cid, 32 * n, hipMemcpyDeviceToHost, s));
     CV_TRY(hipMemcpyAsync(consumed_index, base + o_cix, 4 * n, hipMemcpyDeviceToHost, s));
@@ -303,12 +294,11 @@ int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *
     if (u->resident + n > u->capacity) return CV_E_OOM;
     CV_TRY(hipSetDevice(u->ordinal));
     const size_t bs = (size_t)uniq_bmask(n) + 1;
-    const size_t o_key = 0, o_id = o_key + al16(32 * n), o_ix = o_id + al16(32 * n), o_cal = o_ix + al16(4 * n);
-    const size_t o_bt = o_cal + al16(4 * n), o_rep = o_bt + al16(4 * bs), o_res = o_rep + al16(4 * n);
-    const size_t total = o_res + al16(4 * n) + 16;
-    CV_TRY(u->ws.ensure(total));
+    Layout lay;
+    const size_t o_key = lay.take(32 * n), o_id = lay.take(32 * n), o_ix = lay.take(4 * n), o_cal = lay.take(4 * n);
+    const size_t o_bt = lay.take(4 * bs), o_rep = lay.take(4 * n), o_res = lay.take(4 * n);
+    CV_TRY(u->ws.ensure(lay.top + 16));
     uint8_t *base = u->ws.as<uint8_t>();
-    auto u32 = [base](size_t off) { return reinterpret_cast<uint32_t *>(base + off); };
     hipStream_t s = u->stream;
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
     CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * n, hipMemcpyHostToDevice, s));
@@ -319,14 +309,14 @@ int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *
     if (rc != CV_OK) return rc;
     CvUniqBatch B{};
     B.nstates = (uint32_t)n;
-    B.key = u32(o_key);
-    B.id = u32(o_id);
-    B.cons_index = u32(o_ix);
-    B.caller = u32(o_cal);
-    B.btab = u32(o_bt);
+    B.key = at<uint32_t>(base, o_key);
+    B.id = at<uint32_t>(base, o_id);
+    B.cons_index = at<uint32_t>(base, o_ix);
+    B.caller = at<uint32_t>(base, o_cal);
+    B.btab = at<uint32_t>(base, o_bt);
     B.bmask = (uint32_t)(bs - 1);
-    B.rep = u32(o_rep);
-    B.res = u32(o_res);
+    B.rep = at<uint32_t>(base, o_rep);
+    B.res = at<uint32_t>(base, o_res);
     B.dstat = u->dstat.as<uint32_t>();
     // the check first (a key repeated in the call, or resident): the set changes only after it passed
     CV_TRY(cvk_uniq_load(&u->T, &B, 0, s));

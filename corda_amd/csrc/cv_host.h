@@ -3,7 +3,8 @@
 // statistics, routing (dispatch), and the short slot and workspace helpers (the longer ones — a slot's stream and
 // helper stream, its workspace growth, a verify launch group — serve the core alone and are file-local there).
 // Built on cv_stage.h (host staging, no devices) and cv_launch.h (the kernel launchers); included by cv_api.cpp
-// (the core) and the feature translation units cv_api_sign.cpp, cv_api_pmt.cpp, cv_api_uniq.cpp, cv_api_ck.cpp, cv_api_notary.cpp and cv_api_tearoff.cpp.  The types
+// (the core) and, through cv_batch.h (what the one-shot batch calls share), by the feature translation units
+// cv_api_sign.cpp, cv_api_pmt.cpp, cv_api_uniq.cpp, cv_api_ck.cpp, cv_api_notary.cpp and cv_api_tearoff.cpp.  The types
 // live in namespace cvh (cv_ctx, a global type of the public header, is made of them); nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>

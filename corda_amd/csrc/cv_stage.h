@@ -110,17 +110,18 @@ inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // Host copies into pinned staging.  A large copy is done by the device's worker pool (one core copies
 // ~10-12 GB/s, below what the DMA takes): each segment is cut into 256 KB pieces the workers take in
-// turn.  Copies below 1 MB stay on the calling thread (a notary batch: waking workers costs more).
+// turn.  Copies below par_min in all, 1 MB unless the caller says otherwise, stay on the calling thread (a notary
+// batch: waking workers costs more).
 struct CopyJob {
     void *dst;
     const void *src;
     size_t len;
 };
-inline void par_copy(const std::vector<CopyJob> &jobs, WorkerPool *pool) {
+inline void par_copy(const std::vector<CopyJob> &jobs, WorkerPool *pool, size_t par_min = (size_t)1 << 20) {
     constexpr size_t kPiece = 256 * 1024;
     size_t total = 0;
     for (const CopyJob &j : jobs) total += j.len;
-    if (!pool || pool->threads() <= 1 || total < 4 * kPiece) {
+    if (!pool || pool->threads() <= 1 || total < par_min) {
         for (const CopyJob &j : jobs)
             if (j.len) std::memcpy(j.dst, j.src, j.len);
         return;

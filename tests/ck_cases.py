@@ -404,6 +404,13 @@ CASES: Dict[str, Callable[[], Case]] = {
 }
 
 
+def no_requirements() -> Case:
+    """Transactions none of which has a requirement (nreq = nnodes = nchild = 0: every node-sized piece of the call's
+    buffer is empty): with signers nothing is missing, without any the status is bad signature.  Not in CASES: the
+    tests over CASES assume at least one node."""
+    return Case([Tx([], [key("nr", 0)]), Tx([], []), Tx([], [key("nr", 1), key("nr", 2)])])
+
+
 def mirror_agrees(case: Case) -> bool:
     """fulfilled_ref == crypto.CompositeKey.is_fulfilled_by on every requirement of the case."""
     return all(fulfilled_ref(r, set(tx.signers)) == r.is_fulfilled_by(set(tx.signers)) for tx in case.txs for r in tx.must_sign)

@@ -127,6 +127,24 @@ def make_batch(engine, corpus, ntx, seed=0):
                 resident=resident, expects_resident_conflict=res)
 
 
+def edge_batch(engine, corpus, name):
+    """One-transaction batches at which pieces of the call's one buffer are empty.  "no_inputs": the transaction has
+    leaves and no input state (nstates = 0; for the simple notary).  "no_signatures": a validating call with no
+    signature and no requirement at all (nsig = nreq = nnodes = nchild = 0)."""
+    b = make_batch(engine, corpus, 1)
+    u32 = lambda a: np.array(a, np.uint32)
+    if name == "no_inputs":
+        b["tx_input_count"] = u32([0])
+    elif name == "no_signatures":
+        none = np.zeros((0, 32), np.uint8)
+        b.update(pk=none, sig=np.zeros((0, 64), np.uint8), tx_sig_begin=u32([0, 0]), sig_pre=np.zeros(0, np.uint8),
+                 reqs=(np.zeros(0, np.uint8), none, np.zeros(0, np.int32), u32([0]), u32([]), np.zeros(0, np.int32),
+                       u32([0]), u32([0, 0]), none, np.zeros(0, np.uint8)))
+    else:
+        raise KeyError(name)
+    return b
+
+
 def open_set(engine, batch, capacity=None):
     s = native.UniquenessSet(engine, capacity or (len(batch["resident"][0]) + int(batch["tx_input_count"].sum()) + 8))
     s.load(*batch["resident"])
@@ -158,9 +176,11 @@ def compose(engine, signer, b, validating=True):
     req_missing = np.zeros(0, np.uint8)
     bits, sst, ck = np.ones(nsig, bool), np.zeros(nsig, np.uint8), np.zeros(ntx, np.uint8)
     if validating:
-        bm, sst = engine.verify_batch(b["pk"], b["sig"], ids.reshape(-1), (tx_of * 32).astype(np.uint64),
-                                      np.full(nsig, 32, np.uint32))
-        bits = native.bitmap_to_bools(bm, nsig)
+        bm = np.zeros(0, np.uint64)
+        if nsig:
+            bm, sst = engine.verify_batch(b["pk"], b["sig"], ids.reshape(-1), (tx_of * 32).astype(np.uint64),
+                                          np.full(nsig, 32, np.uint32))
+            bits = native.bitmap_to_bools(bm, nsig)
         r = b["reqs"]
         req_missing, ck = engine.missing_signers(*r[:9], tsb, req_allowed=r[9], bitmap=bm)
     txs = [dict(mstatus=int(mst[t]), recomputed=ids[t].tobytes(), claimed=b["claimed"][t].tobytes(), tx_pre=int(b["tx_pre"][t]),

@@ -13,8 +13,11 @@
 //   dispatch             routing: shard ranges over k devices, per-device exclusion, concurrent callers
 //   mstage_plan/_pack    Merkle staging of a transaction range (non-monotone offsets, empty txs, compact)
 //   cv_tx_verdicts       per-transaction AND
+//   cv_batch.h           what the one-shot batch calls share: Layout against the chained al16 forms, both ranges_ok,
+//                        arena_extent (exact end, a byte past, a wrapping record), Pack / Unpack and par_copy's threshold
 // Exit status 0 = every check passed; sanitizer reports abort the run (halt_on_error).
 #include "../../corda_amd/csrc/cv_api.cpp"
+#include "../../corda_amd/csrc/cv_batch.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -153,6 +156,104 @@ static void test_par_copy() {
                 CHECK(dst[j][jobs[j].len] == 0);              // nothing written past the job
             }
         }
+    }
+}
+
+// par_copy's smallest parallel total: the copies are right on both sides of it, at the default and at the one-upload
+// calls' 4 MB (Pack), with a pool and without; a zero-length put of a null source lists nothing, a get into a null
+// destination or of zero bytes copies nothing
+static void test_pack(int threads) {
+    WorkerPool pool(threads - 1);
+    for (size_t par_min : {(size_t)1 << 20, Pack::kParMin})
+        for (size_t total : {par_min - 1, par_min, par_min + 300001}) {
+            const size_t cut[4] = {0, total / 3, total / 3, total};           // two uneven pieces, an empty one between
+            std::vector<uint8_t> src(total), h(total + 64, 0xEE);
+            for (auto &b : src) b = (uint8_t)rnd();
+            Pack pk{h.data()};
+            for (int j = 0; j < 3; j++) pk.put(cut[j], cut[j + 1] > cut[j] ? &src[cut[j]] : nullptr, cut[j + 1] - cut[j]);
+            pk.put(7, nullptr, 0);
+            CHECK(pk.jobs.size() == 2 && pk.bytes == total);
+            CHECK(pk.wants_pool(threads) == (threads > 1 && total >= Pack::kParMin));
+            CHECK(!pk.wants_pool(1));
+            if (par_min == Pack::kParMin)
+                pk.run(pk.wants_pool(threads) ? &pool : nullptr);
+            else
+                par_copy(pk.jobs, &pool);
+            CHECK(std::memcmp(h.data(), src.data(), total) == 0 && h[total] == 0xEE);
+            std::fill(h.begin(), h.end(), 0xEE);
+            par_copy(pk.jobs, &pool, par_min);                               // the pool given on both sides
+            CHECK(std::memcmp(h.data(), src.data(), total) == 0 && h[total] == 0xEE);
+        }
+    uint8_t back[8] = {1, 2, 3, 4, 5, 6, 7, 8}, dst[4] = {9, 9, 9, 9};
+    const Unpack out{back, 32};                                              // back holds device bytes 32 .. 40
+    out.get(nullptr, 36, 4);
+    out.get(dst, 36, 0);
+    CHECK(dst[0] == 9 && dst[3] == 9);
+    out.get(dst, 36, 3);
+    CHECK(dst[0] == 5 && dst[2] == 7 && dst[3] == 9);
+}
+
+// Layout::take against the chained forms it replaces, over piece sizes that include zeros and non-multiples of 16
+static void test_layout() {
+    for (int rep = 0; rep < 200; rep++) {
+        Layout lay;
+        size_t a = 0, b = 0;          // o_next = al16(o_prev + size)  /  o_next = o_prev + al16(size)
+        for (int k = 0; k < 40; k++) {
+            const size_t size = rnd() % 4 == 0 ? 0 : rnd() % 3 == 0 ? 16 * (rnd() % 9) : rnd() % 100000;
+            const size_t off = lay.take(size);
+            CHECK(off == a && off == b && off % 16 == 0);
+            a = al16(a + size);
+            b += al16(size);
+        }
+        CHECK(lay.top == a && lay.top == b);
+    }
+    uint32_t w[4] = {1, 2, 3, 4};
+    uint8_t *base = reinterpret_cast<uint8_t *>(w);
+    CHECK(at<uint32_t>(base, 8) == w + 2 && *at<uint32_t>(base, 12) == 4 && at<uint8_t>(base, 0) == base);
+}
+
+static void test_ranges() {
+    const uint32_t none[1] = {0}, bad0[1] = {1}, up[4] = {0, 2, 2, 7}, down[4] = {0, 5, 4, 7}, first[4] = {1, 2, 3, 7};
+    CHECK(ranges_ok(none, 0) && ranges_ok(none, 0, 0) && !ranges_ok(none, 0, 1));     // n = 0: begin[0] alone
+    CHECK(!ranges_ok(bad0, 0) && !ranges_ok(bad0, 0, 1));
+    CHECK(ranges_ok(up, 3) && ranges_ok(up, 3, 7) && !ranges_ok(up, 3, 6) && !ranges_ok(up, 3, 8));
+    CHECK(ranges_ok(up, 2, 2) && !ranges_ok(up, 2, 7));
+    CHECK(!ranges_ok(down, 3) && !ranges_ok(down, 3, 7) && ranges_ok(down, 1, 5));    // a descending pair
+    CHECK(!ranges_ok(first, 3) && !ranges_ok(first, 3, 7));                           // a wrong first entry
+}
+
+static void test_extent() {
+    const uint64_t off[5] = {40, 8, 100, 90, UINT64_MAX - 3};
+    const uint32_t len[5] = {10, 0, 28, 39, 4};
+    Extent x = arena_extent(0, 0, nullptr, nullptr, 0);                      // no records
+    CHECK(x.ok && x.lo == 0 && x.hi == 0);
+    x = arena_extent(2, 2, off, len, 0);
+    CHECK(x.ok && x.lo == 0 && x.hi == 0);
+    x = arena_extent(0, 3, off, len, 128);                                   // a record ends exactly at the arena's end
+    CHECK(x.ok && x.lo == 8 && x.hi == 128);
+    x = arena_extent(0, 3, off, len, UINT64_MAX);
+    CHECK(x.ok && x.lo == 8 && x.hi == 128);
+    x = arena_extent(0, 4, off, len, 128);                                   // one a byte past it
+    CHECK(!x.ok && x.lo == 8 && x.hi == 129);
+    CHECK(arena_extent(0, 4, off, len, 129).ok);
+    CHECK(arena_extent(1, 2, off, len, 8).ok && !arena_extent(1, 2, off, len, 7).ok);   // an empty record counts
+    for (uint64_t arena : {(uint64_t)128, (uint64_t)1 << 40, UINT64_MAX}) {  // off + len wraps: never in bounds
+        CHECK(!arena_extent(0, 5, off, len, arena).ok);
+        CHECK(!arena_extent(4, 5, off, len, arena).ok);
+    }
+    // many records (several scan slices), the faulty one anywhere
+    std::vector<uint64_t> o(200000);
+    std::vector<uint32_t> l(o.size(), 16);
+    for (size_t i = 0; i < o.size(); i++) o[i] = 64 + 16 * ((i * 7919) % o.size());
+    const uint64_t end = 64 + 16 * o.size();
+    x = arena_extent(0, o.size(), o.data(), l.data(), end);
+    CHECK(x.ok && x.lo == 64 && x.hi == end);
+    CHECK(!arena_extent(0, o.size(), o.data(), l.data(), end - 1).ok);
+    for (size_t at_i : {(size_t)0, (size_t)65535, (size_t)65536, o.size() - 1}) {
+        const uint64_t keep = o[at_i];
+        o[at_i] = UINT64_MAX - 7;
+        CHECK(!arena_extent(0, o.size(), o.data(), l.data(), UINT64_MAX).ok);
+        o[at_i] = keep;
     }
 }
 
@@ -479,10 +580,14 @@ int main(int argc, char **argv) {
     const bool threads_only = argc > 1 && std::strcmp(argv[1], "--threads") == 0;
     test_pool();
     test_par_copy();
+    for (int threads : {1, 2, 5}) test_pack(threads);
     for (size_t ndev : {1ul, 2ul, 3ul, 8ul}) test_dispatch(ndev, 1, 60);
     test_dispatch(4, 4, 200);        // 4 threads x 200 interleaved calls, 4 devices
     if (!threads_only) {
         test_dedupe();
+        test_layout();
+        test_ranges();
+        test_extent();
         test_stage(false, 3001);
         test_stage(true, 3001);
         test_stage(false, 140001);   // several range-scan slices

@@ -261,6 +261,14 @@ def refused(kind, seed):
     return one_leaf(seed, known=False)
 
 
+def edge_batches():
+    """Small batches at which pieces of the calls' one buffer are empty or nothing is signed: one tear-off with no
+    leaf and no node at all (L = M = 0), the same beside two ordinary ones, and three tear-offs all refused."""
+    bare = {"leaves": [], "nodes": ([], [], [], []), "root": bytes(range(32)), "tree": None}
+    return {"bare": [bare], "bare_between": [one_leaf(21), bare, refused(UNKNOWN, 22)],
+            "three_refused": [refused(NO_LEAVES, 31), refused(VERIFY_FAILED, 32), refused(WRONG_COMMAND, 33)]}
+
+
 def service_batch(ntx, seed=0):
     """ntx tear-offs, roughly 1 in 8 refused, cycling through outcomes 1 to 6; up to 64 the accepted ones are
     tear-offs of 6-leaf transactions with 2 kept commands, above that one-node trees."""

@@ -44,6 +44,20 @@ def test_req_allowed_null_means_none(engine, built):
     assert st.tolist() == [C.VS_MISSING if (want_missing[trb[t]:trb[t + 1]] == 1).any() else C.VS_OK for t in range(len(trb) - 1)]
 
 
+@pytest.mark.parametrize("wide_min", C.WIDE_MINS)
+def test_no_requirements_at_all(engine, wide_min):
+    """nreq = nnodes = nchild = 0, with req_allowed and verdict_bitmap NULL and with both given."""
+    f, want_missing, want_status = C.build(C.no_requirements())
+    assert f["kind"].size == 0 and want_missing.size == 0 and want_status.tolist() == [C.VS_OK, C.VS_BAD_SIGNATURE, C.VS_OK]
+    nsig = int(f["tx_sig_begin"][-1])
+    for opt in ({}, {"req_allowed": f["req_allowed"], "bitmap": C.all_ones(nsig)}):
+        rm, st = engine.missing_signers(*[f[k] for k in FLAT], wide_min=wide_min, **opt)
+        assert rm.size == 0 and st.tolist() == want_status.tolist(), (wide_min, sorted(opt))
+    f, _, want_status = C.build(C.Case(C.no_requirements().txs, bitmap=C.ones_except(1)))   # the last one's first signature
+    _, st = engine.missing_signers(*[f[k] for k in FLAT], bitmap=f["bitmap"], wide_min=wide_min)
+    assert st.tolist() == want_status.tolist() == [C.VS_OK, C.VS_BAD_SIGNATURE, C.VS_BAD_SIGNATURE]
+
+
 def _up(a) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(DEV)
 

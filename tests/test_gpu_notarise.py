@@ -3,8 +3,9 @@ existing calls on the same inputs (tests/notarise_batches.py: Merkle ids -> veri
 the restatement's gate -> cv_uniq_commit_batch on a second set loaded identically, keys = hashlib.sha256(leaf) ->
 cv_ed25519_sign_keyed).  Every comparison is exact, array for array; signing is deterministic.
 
-Shapes: ntx 1, 63, 64, 65, 130, 257 and 1100 (past the finalise scan's workgroup of 1024), 1 to 3 signatures a
-transaction so that ranges straddle bitmap words, 0 to 4 leaves and 0 to 3 inputs, a set loaded with a few states.
+Shapes: ntx 1, 2 (the second transaction without leaves), 63, 64, 65, 130, 257 and 1100 (past the finalise scan's
+workgroup of 1024), 1 to 3 signatures a transaction so that ranges straddle bitmap words, 0 to 4 leaves and 0 to 3
+inputs, a set loaded with a few states.
 """
 import numpy as np
 import pytest
@@ -15,7 +16,7 @@ from corda_amd import native
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = (1, 63, 64, 65, 130, 257, 1100)
+SHAPES = (1, 2, 63, 64, 65, 130, 257, 1100)
 NAMES = ("outcome", "ids", "notary_sig", "first_bad", "req_missing", "state_conflict", "consumed_id", "consumed_index",
          "consumed_caller")
 
@@ -89,6 +90,24 @@ def test_not_validating(engine, corpus, signer, ntx):
     bad = [t for t, k in enumerate(b["kind"]) if k in ("tx_invalid", "bad_key", "missing", "malformed", "prefilter")]
     assert bad and (got["outcome"][bad] == C.SUCCESS).all()      # their inputs are fresh: committed, as the reference does
     assert (got["first_bad"] == native.NS_NO_SIG).all()
+    uniq.close()
+
+
+@pytest.mark.parametrize("name,validating", (("no_inputs", False), ("no_signatures", True)))
+def test_one_transaction_with_empty_pieces(engine, corpus, signer, name, validating):
+    """ntx = 1 where whole groups of the call's arrays are empty: no input state under the simple notary (committed,
+    nothing resident afterwards but what was loaded), and a validating call without any signature or requirement (the
+    reference's SignedTransaction without signatures: TX_INVALID, no signature to name)."""
+    b = B.edge_batch(engine, corpus, name)
+    want, ref_set = B.compose(engine, signer, b, validating)
+    uniq = B.open_set(engine, b)
+    got = B.call(engine, uniq, signer, b, validating=validating)
+    assert_same(got, want, name)
+    assert B.same_sets(uniq, ref_set, np.concatenate([B.state_keys(b), b["resident"][0]]))
+    assert got["outcome"].tolist() == [C.TX_INVALID if validating else C.SUCCESS]
+    assert got["first_bad"].tolist() == [native.NS_NO_SIG] and got["notary_sig"].any() == (not validating)
+    assert got["state_conflict"].size == (0 if name == "no_inputs" else int(b["tx_input_count"][0]))
+    ref_set.close()
     uniq.close()
 
 

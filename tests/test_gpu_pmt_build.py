@@ -59,6 +59,21 @@ def test_batch_feeds_verify_unchanged(engine, built):
     assert np.array_equal(ids, b["ids"])
 
 
+@pytest.mark.parametrize("ntx", [1, 3])
+def test_transactions_without_leaves_alone(engine, ntx):
+    """A batch with no leaf and no include at all: the build emits no node (every leaf-, include- and node-sized piece
+    of its buffer is empty), and cv_partial_merkle_verify over that output runs with nnodes = 0 and ncheck = 0."""
+    b = C.batch_of([([], [], None)] * ntx)
+    assert b["status"].tolist() == [C.EMPTY] * ntx and b["kind"].size == 0 and b["tree_begin"].tolist() == [0] * (ntx + 1)
+    got = engine.partial_merkle_build(b["leaf_hash"], b["txb"], b["include"], b["inc_begin"])
+    for name, a in zip(("kind", "left", "right", "node_hash", "tree_begin", "ids", "status"), got):
+        assert a.shape == b[name].shape and np.array_equal(a, b[name]), name
+    kind, left, right, node_hash, tb, ids, _ = got
+    v, vst = engine.partial_merkle_verify(kind, left, right, node_hash, tb, ids, b["include"], b["inc_begin"])
+    want = [M.verify_flat([], [], [], [], 0, 0, bytes(32), [])] * ntx         # (0, 2): no nodes are no tree encoding
+    assert list(zip(v.tolist(), vst.tolist())) == want
+
+
 def test_ids_equal_merkle_tx_ids(engine):
     """cv_filtered_build's ids = cv_merkle_tx_ids_ex over the same leaf blobs (no-leaf transactions included)."""
     rng = random.Random(5)

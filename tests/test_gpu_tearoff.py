@@ -186,6 +186,31 @@ def test_fused_call_equals_the_composition(engine, signer, ntx):
     assert bits.all()
 
 
+@pytest.mark.parametrize("name", list(C.edge_batches()))
+def test_edge_batches_equal_the_composition_and_the_oracle(engine, signer, name):
+    """ntx = 1 with no leaf and no node, the same between two ordinary tear-offs, and three tear-offs none of which is
+    accepted (nothing is signed): the verify against the two-step path, the signing call against the composition,
+    both against the restatement; then with leaf_pre NULL."""
+    txs = C.edge_batches()[name]
+    f, want = C.flatten(txs), C.expected(txs)
+    if name == "three_refused":
+        assert not want["accepted"].size
+    v, st = engine.filtered_verify(*verify_args(f))
+    v2, st2 = two_step(engine, f)
+    assert np.array_equal(v, v2) and np.array_equal(st, st2)
+    assert np.array_equal(v, want["verdict"]) and np.array_equal(st, want["status"])
+    out, fb, sig = engine.tearoff_sign_batch(signer, *verify_args(f), f["leaf_pre"])
+    c_out, c_fb, c_sig = compose(engine, signer, f)
+    assert np.array_equal(out, c_out) and np.array_equal(fb, c_fb) and np.array_equal(sig, c_sig)
+    assert np.array_equal(out, want["outcome"]) and np.array_equal(fb, want["first_bad"])
+    assert not sig[out != C.SUCCESS].any()
+    for t in want["accepted"]:
+        assert sig[t].tobytes() == ed25519_ref.sign(SEED, f["root"][t].tobytes())
+    out, fb, sig = engine.tearoff_sign_batch(signer, *verify_args(f), None)
+    c_out, c_fb, c_sig = compose(engine, signer, f, with_pre=False)
+    assert np.array_equal(out, c_out) and np.array_equal(fb, c_fb) and np.array_equal(sig, c_sig)
+
+
 def test_null_leaf_pre_and_null_first_bad(engine, signer):
     txs = C.service_batch(65, seed=7)
     f = C.flatten(txs)

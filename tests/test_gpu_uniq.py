@@ -61,6 +61,16 @@ def test_default_rounds_and_null_enable(engine):
         assert s.stats()["rounds"] == DEFAULT_ROUNDS
 
 
+@pytest.mark.parametrize("max_rounds", [0, DEFAULT_ROUNDS])
+def test_a_batch_without_states(engine, max_rounds):
+    """nstates = 0: all three requests decided (two accepted, the disabled one skipped), nothing resident; the set then
+    takes a batch with states as usual."""
+    with native.UniquenessSet(engine, 64) as s:
+        s.set_max_rounds(max_rounds)
+        oracle = C.run_case(C.no_states(), _commit(s), s.lookup, ("no_states", max_rounds))
+        assert s.stats()["resident"] == len(oracle.committed) == 1
+
+
 def test_large_batch(engine):
     """20,000 requests x 2 states with 5 % reuse in one call: many blocks, rounds that end by the device counter."""
     case = C.big_batch()

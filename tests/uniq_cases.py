@@ -102,6 +102,14 @@ CASES = {"reference": reference_scenarios, "random": random_carry_over, "chain":
          "near_keys": near_keys, "state_counts": state_counts}
 
 
+def no_states():
+    """A batch whose requests have no states at all (nstates = 0: every state-sized piece of the call's workspace is
+    empty), one of them disabled, then a batch with states on the same set.  Not in CASES: nothing is ever probed."""
+    return [[([], tx_id_of("h", t), t, t != 1) for t in range(3)],
+            [([key_of("h", 0)], tx_id_of("h", 3), 3, True), ([], tx_id_of("h", 4), 4, True),
+             ([key_of("h", 0), key_of("h", 1)], tx_id_of("h", 5), 5, True)]]
+
+
 def big_batch(ntx=20000, seed=7):
     """20,000 requests x 2 states with 5 % reuse: a state is, with probability 0.05, one an earlier request used."""
     rng = random.Random(seed)
