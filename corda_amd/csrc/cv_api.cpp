@@ -4,8 +4,8 @@
 // buffers) for plain, keyed, Merkle and transaction batches with synchronous and asynchronous forms, tickets, the
 // device-resident verify and Merkle entry points used by bench.py, and calibration.  The engine state is
 // cv_host.h's, the staging logic cv_stage.h's; signing (cv_api_sign.cpp), partial Merkle trees (cv_api_pmt.cpp)
-// the uniqueness set (cv_api_uniq.cpp), missing signers (cv_api_ck.cpp) and the notary's fused call (cv_api_notary.cpp)
-// are translation units of their own.
+// the uniqueness set (cv_api_uniq.cpp), missing signers (cv_api_ck.cpp), the notary's fused call (cv_api_notary.cpp),
+// the tear-off calls (cv_api_tearoff.cpp) and the resolve call (cv_api_resolve.cpp) are translation units of their own.
 #include "cv_host.h"
 
 using namespace cvh;
@@ -81,6 +81,14 @@ static hipError_t launch_verify(Device &d, const CvkPlan &plan, Slot &sl, uint32
                    sl.ws_dig.as<uint32_t>(), sl.ws_cap, s, ev, split && sl.split.s2 ? &sl.split : nullptr, po);
     const hipError_t e2 = ws_end(sl, s);
     return e != hipSuccess ? e : e2;
+}
+
+// cv_ed25519_verify_device's launch group for a caller that already holds d.mu (cv_api_resolve.cpp, under dispatch_one)
+hipError_t cvh::verify_device_locked(cv_ctx *ctx, Device &d, size_t n, const uint8_t *pk, const uint8_t *sig,
+                                     const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t *bitmap,
+                                     uint8_t *status, hipStream_t s) {
+    return launch_verify(d, ctx->opts().plan, pick_slot(d, s), (uint32_t)n, pk, sig, arena, off, len, bitmap, status, s,
+                         nullptr, true);
 }
 
 extern "C" {
@@ -165,6 +173,9 @@ int cv_diag_stats(cv_ctx *ctx, int which, double *out, size_t nout, int reset) {
     } else if (which == CV_STATS_TIMELINE) {
         for (int k = 0; k <= kTlVals; k++) v[k] = s.tl[k];
         nv = kTlVals + 1;
+    } else if (which == CV_STATS_RESOLVE) {
+        for (int k = 0; k <= kRsVals; k++) v[k] = s.rs[k];
+        nv = kRsVals + 1;
     } else {
         return CV_E_ARGS;
     }
@@ -178,6 +189,8 @@ int cv_diag_stats(cv_ctx *ctx, int which, double *out, size_t nout, int reset) {
             s.small_calls = 0;
         } else if (which == CV_STATS_TIMELINE) {
             std::fill(s.tl, s.tl + kTlVals + 1, 0.0);
+        } else if (which == CV_STATS_RESOLVE) {
+            std::fill(s.rs, s.rs + kRsVals + 1, 0.0);
         } else {
             s.calls = s.routed_whole = s.split_calls = s.shards = s.keyed_calls = s.keyed_chunks = s.merkle_calls =
                 s.merkle_chunks = 0;

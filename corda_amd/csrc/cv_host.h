@@ -4,8 +4,9 @@
 // helper stream, its workspace growth, a verify launch group — serve the core alone and are file-local there).
 // Built on cv_stage.h (host staging, no devices) and cv_launch.h (the kernel launchers); included by cv_api.cpp
 // (the core) and, through cv_batch.h (what the one-shot batch calls share), by the feature translation units
-// cv_api_sign.cpp, cv_api_pmt.cpp, cv_api_uniq.cpp, cv_api_ck.cpp, cv_api_notary.cpp and cv_api_tearoff.cpp.  The types
-// live in namespace cvh (cv_ctx, a global type of the public header, is made of them); nothing here is exported.
+// cv_api_sign.cpp, cv_api_pmt.cpp, cv_api_uniq.cpp, cv_api_ck.cpp, cv_api_notary.cpp, cv_api_tearoff.cpp and
+// cv_api_resolve.cpp.  The types live in namespace cvh (cv_ctx, a global type of the public header, is made of
+// them); nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -137,6 +138,7 @@ constexpr int kRing = 16;
 constexpr int kStage = 6;       // pinned host staging blocks (pageable inputs are packed into them)
 constexpr int kOuts = 4;        // pipelined host calls in flight per device (async verify + Merkle calls)
 constexpr size_t kFailKeep = 1024;   // failed asynchronous calls remembered per output (PipeOut::failed)
+constexpr int kRsVals = 8;           // CV_STATS_RESOLVE values per timed cv_resolve_batch call
 constexpr int kTlVals = 14;          // CV_STATS_TIMELINE values per timed call (PipeOut::tl_sum)
 
 // The output of one pipelined host call on one device: its results on the device (dout), the pinned
@@ -257,8 +259,8 @@ struct Device {
     PinBuf zc_in, zc_out;
     DevBuf pmt;                          // partial Merkle trees: inputs, outputs and workspace, packed
     DevBuf ck;                           // missing signers (cv_api_ck.cpp): inputs, outputs and workspace, packed
-    // tear-off verify and signing (cv_api_tearoff.cpp): a call's inputs packed for ONE upload into d.pmt, and the
-    // block its outputs come back through
+    // tear-off verify and signing (cv_api_tearoff.cpp) and cv_resolve_batch (cv_api_resolve.cpp): a call's inputs
+    // packed for ONE upload into d.pmt, and the block its outputs come back through
     PinBuf ts_in, ts_out;
     Slot slot[kSlots];
     uint64_t clock = 0;
@@ -367,6 +369,7 @@ struct Stats {
     uint64_t calls = 0, routed_whole = 0, split_calls = 0, shards = 0, keyed_calls = 0, keyed_chunks = 0,
              merkle_calls = 0, merkle_chunks = 0;
     double tl[kTlVals + 1] = {};   // CV_STATS_TIMELINE sums (PipeOut::tl_sum) + calls
+    double rs[kRsVals + 1] = {};   // CV_STATS_RESOLVE sums + calls
 };
 
 inline int hip_rc(hipError_t e) {
@@ -524,6 +527,12 @@ int uniq_stat_begin(cv_uniq *u);
 int uniq_stat_end(cv_uniq *u);
 uint32_t uniq_bmask(size_t nstates);
 int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, uint64_t *rounds);
+
+// cv_api.cpp: one verify launch group of n signatures (device pointers, as cv_ed25519_verify_device) on stream s of
+// device d, ordered on the shared verify workspace; the caller holds d.mu
+hipError_t verify_device_locked(cv_ctx *ctx, Device &d, size_t n, const uint8_t *pk, const uint8_t *sig,
+                                const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t *bitmap,
+                                uint8_t *status, hipStream_t s);
 
 inline Device *find_dev(cv_ctx *ctx, int device) {
     for (auto &d : ctx->devs)

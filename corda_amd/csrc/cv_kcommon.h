@@ -11,6 +11,7 @@
 //   cv_k_ck.hip    missing signers (cv_ck.h): one lane per transaction, one wave per large transaction
 //   cv_k_notary.hip the notary's fused commit step (cv_notary.h): gate, state-key gather, finalise + list, scatter
 //   cv_k_tearoff.hip the tear-off verifier and the oracle's signing step (cv_tearoff.h): check bytes, gate, compaction
+//   cv_k_resolve.hip the graph steps of cv_resolve_batch (cv_resolve.h): join-table insert, probe, gate
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +23,7 @@
 #include "cv_ck.h"
 #include "cv_notary.h"
 #include "cv_tearoff.h"
+#include "cv_resolve.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -194,6 +196,10 @@ __global__ void cv_notary_scatter_kernel(uint32_t count, const uint32_t *list, c
 __global__ void cv_tearoff_check_kernel(CvTearoff T);
 __global__ void cv_tearoff_gate_kernel(CvTearoff T);
 __global__ void cv_tearoff_compact_kernel(CvTearoff T, uint32_t *count);
+// the graph steps of cv_resolve_batch (cv_k_resolve.hip, cv_resolve.h)
+__global__ void cv_resolve_insert_kernel(CvResolve R);
+__global__ void cv_resolve_probe_kernel(CvResolve R);
+__global__ void cv_resolve_gate_kernel(CvResolve R);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

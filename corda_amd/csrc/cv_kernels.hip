@@ -466,6 +466,20 @@ hipError_t cvk_tearoff_compact(const CvTearoff *T, uint32_t *count, hipStream_t 
     return hipGetLastError();
 }
 
+// ---- the graph steps of cv_resolve_batch (cv_resolve.h).  Counts are at most 2^30 (the host's check).
+hipError_t cvk_resolve_join(const CvResolve *R, hipStream_t stream) {
+    if (!R || R->ntx == 0 || !R->tab) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_resolve_insert_kernel, uniq_grid(R->ntx), dim3(CV_BLOCK), 0, stream, *R);
+    if (R->ninputs) hipLaunchKernelGGL(cv_resolve_probe_kernel, uniq_grid(R->ninputs), dim3(CV_BLOCK), 0, stream, *R);
+    return hipGetLastError();
+}
+
+hipError_t cvk_resolve_gate(const CvResolve *R, hipStream_t stream) {
+    if (!R || R->ntx == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_resolve_gate_kernel, uniq_grid(R->ntx), dim3(CV_BLOCK), 0, stream, *R);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

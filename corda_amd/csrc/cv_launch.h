@@ -7,6 +7,7 @@
 #include "cv_ck.h"
 #include "cv_notary.h"
 #include "cv_tearoff.h"
+#include "cv_resolve.h"
 #include "cv_uniq.h"
 
 // Helper stream and events of one verify workspace slot, used by cvk_verify's drain overlap (a
@@ -117,6 +118,13 @@ hipError_t cvk_notary_scatter(uint32_t count, const uint32_t *list, const uint8_
 hipError_t cvk_tearoff_check(const CvTearoff *T, hipStream_t stream);
 hipError_t cvk_tearoff_gate(const CvTearoff *T, hipStream_t stream);
 hipError_t cvk_tearoff_compact(const CvTearoff *T, uint32_t *count, hipStream_t stream);
+// The graph steps of cv_resolve_batch (cv_resolve.h; kernels in cv_k_resolve.hip), enqueued on `stream`, nothing
+// synchronised.  join: one lane per transaction inserts its claimed id into R->tab (all CVR_NONE before; R->dstat at
+// its start values), then one lane per input probes it -> input_dep, input_status (ninputs == 0 launches the insert
+// alone: the duplicate check is its work).  gate: one lane per transaction, after the Merkle, verify and
+// missing-signers stages -> outcome, first_bad, bad_input and the counters.  Counts are at most 2^30.
+hipError_t cvk_resolve_join(const CvResolve *R, hipStream_t stream);
+hipError_t cvk_resolve_gate(const CvResolve *R, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

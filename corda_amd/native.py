@@ -42,6 +42,12 @@ CV_NS_BAD_KEY, CV_NS_SIGNATURES_MISSING, CV_NS_MALFORMED, CV_NS_CONFLICT = 5, 6,
 # cv_tearoff_sign_batch outcome[t] (CV_TS_*), its leaf_pre codes and first_bad's "no leaf"
 CV_TS_SUCCESS, CV_TS_NO_LEAVES, CV_TS_MALFORMED, CV_TS_VERIFY_FAILED = 0, 1, 2, 3
 CV_TS_NOT_COMMANDS, CV_TS_WRONG_COMMAND, CV_TS_UNKNOWN = 4, 5, 6
+# cv_resolve_batch outcome[t] (CV_RS_*), graph[CV_RG_STATUS] (CV_RG_*) and the words of graph (RG_*)
+CV_RS_OK, CV_RS_EMPTY, CV_RS_ID_MISMATCH, CV_RS_TX_INVALID, CV_RS_BAD_KEY = 0, 1, 2, 4, 5
+CV_RS_SIGNATURES_MISSING, CV_RS_MALFORMED, CV_RS_BAD_INPUT, CV_RS_UNRESOLVED = 6, 7, 9, 10
+CV_RG_OK, CV_RG_BAD_ID, CV_RG_DUPLICATE_ID = 0, 1, 2
+RG_WORDS = ("status", "which", "n_pass", "stop_class", "stop_tx", "stop_input", "external", "maxprobe", "wraps")
+RS_NONE = 0xFFFFFFFF              # input_dep: not in the batch; bad_input, graph: none
 TS_PRE_OK, TS_PRE_NOT_COMMAND, TS_PRE_WRONG_COMMAND, TS_PRE_UNKNOWN = 0, 1, 2, 3
 TS_NO_LEAF = 0xFFFFFFFF
 NS_NO_SIG = 0xFFFFFFFF            # first_bad: no signature of the transaction settled its outcome
@@ -65,7 +71,7 @@ EXPORTED = (
     "cv_uniq_open", "cv_uniq_close", "cv_uniq_reserve", "cv_uniq_commit_batch", "cv_uniq_lookup", "cv_uniq_load",
     "cv_uniq_set_max_rounds", "cv_uniq_stats",
     "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
-    "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch",
+    "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch", "cv_resolve_batch",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -81,7 +87,9 @@ STATS = {"pipe": (0, ("plan_s", "pack_s", "wait_s", "enqueue_s", "sync_s", "call
                        "merkle_calls", "merkle_subchunks")),
          "timeline": (3, ("ramp_ms", "dma_end_ms", "span_ms", "busy_ms", "idle_ms", "tail_ms", "result_copy_ms",
                           "first_subchunk", "merkle_busy_ms", "verify_busy_ms", "merkle_dma_end_ms", "groups",
-                          "host_pre_ms", "host_post_ms", "calls"))}
+                          "host_pre_ms", "host_post_ms", "calls")),
+         "resolve": (4, ("upload_ms", "merkle_ms", "join_ms", "verify_ms", "signers_ms", "gate_ms", "readback_ms",
+                         "host_order_ms", "calls"))}
 
 
 class NativeUnavailable(RuntimeError):
@@ -215,6 +223,9 @@ def load():
         lib.cv_filtered_verify.restype = ctypes.c_int
         lib.cv_tearoff_sign_batch.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp, _sz] + [_vp] * 10
         lib.cv_tearoff_sign_batch.restype = ctypes.c_int
+        lib.cv_resolve_batch.argtypes = ([_vp, _sz, _vp, ctypes.c_uint64] + [_vp] * 8 + [_sz] * 3 + [_vp] * 9 + [_sz] +
+                                         [_vp] * 4 + [ctypes.c_uint64] + [_vp] * 9)
+        lib.cv_resolve_batch.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp]
         lib.cv_ed25519_sign_keyed.restype = ctypes.c_int
         lib.cv_ed25519_sign_keyed_device.argtypes = [_vp, ctypes.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]
@@ -825,6 +836,68 @@ class Engine:
             self._merkle_args(arena, leaf_off, leaf_len, txb, scan=True)   # leaves past the arena: ValueError
         _check(rc, "cv_tearoff_sign_batch")
         return outcome[:ntx], None if first_bad is None else first_bad[:ntx], sig[:ntx]
+
+    RESOLVE_OUTPUTS = ("outcome", "first_bad", "req_missing", "bad_input", "input_dep", "input_status", "order", "graph",
+                       "ids")
+
+    def resolve_batch(self, arena, leaf_off, leaf_len, tx_leaf_begin, claimed_id, sigs, reqs, tx_input_begin,
+                      input_txhash, input_index, tx_output_count, seed: int = 0, out=None) -> dict:
+        """cv_resolve_batch: ResolveTransactionsFlow.call over the downloaded transactions, in download order, in one
+        call (ids, signatures, missing signers, the join of every input against the batch, the duplicate check,
+        topologicalSort and the walk to its first failure).  Leaves as merkle_tx_ids; claimed_id (ntx,32) u8;
+        sigs = (pk (nsig,32), sig (nsig,64), tx_sig_begin u32[ntx+1], sig_pre u8[nsig] or None); reqs = the arrays of
+        missing_signers up to sig_key: (kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin,
+        sig_key); the graph: tx_input_begin u32[ntx+1], input_txhash (ninputs,32) u8, input_index u32[ninputs],
+        tx_output_count u32[ntx]; seed 0 draws a fresh one.  Returns a dict of RESOLVE_OUTPUTS
+        (include/cordaverify.h; graph u32[9], see RG_WORDS).  out: arrays to write into by name; an optional output
+        (first_bad, req_missing, ids) given as None is passed as NULL and comes back None."""
+        def arr(a, dt, n, what, width=1):
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+            if a.size != n * width:
+                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
+            return a if a.size else np.zeros(width, dt)
+        ntx, arena, leaf_off, leaf_len, tx_leaf_begin = self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
+        if ntx < 0:
+            raise ValueError("tx_leaf_begin must have ntx + 1 entries")
+        claimed_id = arr(claimed_id, np.uint8, ntx, "claimed_id", 32)
+        pk, sg, tsb, sig_pre = sigs
+        tsb = arr(tsb, np.uint32, ntx + 1, "tx_sig_begin")
+        nsig = int(tsb[-1])
+        kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key = reqs
+        tx_req_begin = arr(tx_req_begin, np.uint32, ntx + 1, "tx_req_begin")
+        req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32).reshape(-1)
+        child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32).reshape(-1)
+        nreq, nnodes = req_begin.size - 1, child_begin.size - 1
+        child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
+        nchild = child.size
+        if nreq < 0 or nnodes < 0:
+            raise ValueError("the begin arrays must have count + 1 entries")
+        a_sig = [arr(pk, np.uint8, nsig, "pk", 32), arr(sg, np.uint8, nsig, "sig", 64), tsb,
+                 None if sig_pre is None else arr(sig_pre, np.uint8, nsig, "sig_pre")]
+        a_req = [arr(kind, np.uint8, nnodes, "kind"), arr(leaf_key, np.uint8, nnodes, "leaf_key", 32),
+                 arr(threshold, np.int32, nnodes, "threshold"), child_begin, child if nchild else np.zeros(1, np.uint32),
+                 arr(weight, np.int32, nchild, "weight"), req_begin, tx_req_begin, arr(sig_key, np.uint8, nsig, "sig_key", 32)]
+        tib = arr(tx_input_begin, np.uint32, ntx + 1, "tx_input_begin")
+        nin = int(tib[-1])
+        a_graph = [tib, arr(input_txhash, np.uint8, nin, "input_txhash", 32), arr(input_index, np.uint32, nin, "input_index"),
+                   arr(tx_output_count, np.uint32, ntx, "tx_output_count")]
+        m, q = max(nin, 1), max(ntx, 1)
+        fresh = {"outcome": lambda: np.zeros(q, np.uint8), "first_bad": lambda: np.zeros(q, np.uint32),
+                 "req_missing": lambda: np.zeros(max(nreq, 1), np.uint8), "bad_input": lambda: np.zeros(q, np.uint32),
+                 "input_dep": lambda: np.zeros(m, np.uint32), "input_status": lambda: np.zeros(m, np.uint8),
+                 "order": lambda: np.zeros(q, np.uint32), "graph": lambda: np.zeros(len(RG_WORDS), np.uint32),
+                 "ids": lambda: np.zeros((q, 32), np.uint8)}
+        out = dict(out or {})
+        o = [out[k] if k in out else fresh[k]() for k in self.RESOLVE_OUTPUTS]
+        rc = self._lib.cv_resolve_batch(self._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len), _p(tx_leaf_begin),
+                                        _p(claimed_id), *[_p(a) for a in a_sig], nreq, nnodes, nchild,
+                                        *[_p(a) for a in a_req], nin, *[_p(a) for a in a_graph], ctypes.c_uint64(seed),
+                                        *[_p(a) for a in o])
+        if rc == -3:
+            self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
+        _check(rc, "cv_resolve_batch")
+        cut = {"req_missing": nreq, "input_dep": nin, "input_status": nin, "graph": len(RG_WORDS)}
+        return {k: None if a is None else a[:cut.get(k, ntx)] for k, a in zip(self.RESOLVE_OUTPUTS, o)}
 
     # ------------------------------------------------------------ device-resident API
     def missing_signers_device(self, device: int, ntx: int, nreq: int, nnodes: int, nchild: int, nsig: int, d_kind: int,

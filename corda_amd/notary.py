@@ -20,8 +20,9 @@ every signature of every transaction — sharded over the ranks of a process gro
 each rank verifying its 64-aligned slice on its own GPU and ONE all-gather (RCCL under the "nccl"
 backend) replicating the verdict and key-status bitmaps into the commit step — then inputs are
 committed in request order (so conflicts resolve exactly as sequential flows would) and the notary
-signs every accepted id and every conflict report in ONE GPU signing call.  Contract verification
-and dependency resolution (ResolveTransactionsFlow) are out of scope.
+signs every accepted id and every conflict report in ONE GPU signing call.  Contract verification is
+out of scope; dependency resolution (ResolveTransactionsFlow) is corda_amd.resolve's
+(DESIGN.md §5.13), not this mirror's.
 
 A request that the reference answers with a Result carries `error` (a NotaryError); one whose flow
 the reference fails by an exception carries `failure` (that exception) instead — the client sees

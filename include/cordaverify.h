@@ -60,6 +60,11 @@
  *                                 SignedTransaction.kt:34-38,58-93: ids, signatures, missing signers, the commit and
  *                                 the notary's signatures for a whole batch in one call, the reference's outcome and
  *                                 precedence settled in the library
+ *   cv_resolve_batch          1 x  ResolveTransactionsFlow.call over the downloaded transactions
+ *                                 core/src/main/kotlin/net/corda/flows/ResolveTransactionsFlow.kt:37-67,96-111,170,
+ *                                 SignedTransaction.kt:34-38,58-93,134, ServiceHub.kt:46-49: ids, signatures, missing
+ *                                 signers, the join of every input against the batch, the duplicate check,
+ *                                 topologicalSort and the ordered walk up to its first failure in one call
  *
  * Conventions
  *   - Return codes: CV_OK (0) or a negative CV_E* code; nothing throws, aborts or longjmps across
@@ -633,6 +638,106 @@ int cv_tearoff_sign_batch(cv_ctx *ctx, const cv_signer *s, size_t ntx,
     const uint8_t *leaf_pre /* nleaves, NULL = none: the service's verdict on each filtered leaf's CONTENT */,
     uint8_t *outcome /* ntx */, uint32_t *first_bad /* ntx, optional */, uint8_t *sig_out /* ntx*64 */);
 
+/* The body of ResolveTransactionsFlow.call (core/src/main/kotlin/net/corda/flows/ResolveTransactionsFlow.kt:96-111)
+ * over the ntx transactions downloadDependencies returned, in ONE call.  The transactions are given in DOWNLOAD ORDER,
+ * the order of resultQ.values (:150,:170): topologicalSort's result depends on it.  The binding decodes the StateRefs
+ * (Kryo stays on the JVM) and passes, per input, its txhash and index, and per transaction its number of outputs; the
+ * leaves are not decoded here.
+ *   :39-45  forwardGraph: input_dep[i] = the transaction of the batch whose CLAIMED id (stx.id, the key of resultQ)
+ *           equals input_txhash[i], or 0xffffffff: not in the batch — by construction of downloadDependencies
+ *           (:158-174) a transaction the node already stores; that lookup stays with the binding.
+ *   :167,:41 `stx.tx` of every download is touched before anything is verified: one transaction that is CV_RS_EMPTY or
+ *           CV_RS_ID_MISMATCH fails the flow as a whole, graph[CV_RG_STATUS] = CV_RG_BAD_ID.
+ *   :170,:65 check(putIfAbsent == null), require(result.size == transactions.size): two transactions with one id,
+ *           CV_RG_DUPLICATE_ID.  CV_RG_BAD_ID takes precedence: the download rounds, which are not an input here,
+ *           could meet the two in either order, and both fail the flow.
+ *   :37-67  topologicalSort: order[] is its result, element for element (the dependents of a transaction distinct and
+ *           in download order, the LinkedHashSet of :43; visit in download order; post-order, reversed).
+ *   :105-111 the walk over order: stx.toLedgerTransaction(serviceHub) is verifySignatures() WITHOUT allowed keys
+ *           (SignedTransaction.kt:134 -> :58-72: checkSignaturesAreValid, then the missing signers), then every input
+ *           through loadState (ServiceHub.kt:46-49), in order: a dependency in the batch that was not recorded before
+ *           — it does not stand earlier in order; only a self-reference or a cycle of hand-fed input_txhash gets
+ *           there — is a TransactionResolutionException, CV_RS_UNRESOLVED; one that was, with
+ *           tx_output_count[dep] <= input_index, makes `outputs[stateRef.index]` throw, CV_RS_BAD_INPUT.  The walk
+ *           stops at the first transaction that fails.  ltx.verify() (:108, the contracts) and recordTransactions
+ *           (:109) are NOT run here: the binding runs them for the graph[CV_RG_N_PASS] leading transactions of order.
+ *   :119-125 the final single stx / wtx is one transaction that is not recorded; it stays with the binding.
+ * outcome[t], the verdict of transaction t on its own, whatever the order; first match wins:
+ *     1. CV_RS_EMPTY, CV_RS_ID_MISMATCH                 as CV_NS_*
+ *     2. CV_RS_TX_INVALID, CV_RS_BAD_KEY                the FIRST failing signature in order settles the class, as in
+ *        cv_notarise_batch (sig_pre likewise); no signatures at all is CV_RS_TX_INVALID, the rule of cv_tx_verdicts
+ *        (the reference cannot construct one, SignedTransaction.kt:28).  Signatures are verified over the id
+ *        recomputed on the device: past class 1 it equals the claimed id the reference verifies over.
+ *     3. CV_RS_MALFORMED, CV_RS_SIGNATURES_MISSING      cv_missing_signers over the same batch, nothing allowed
+ *     4. CV_RS_BAD_INPUT                                some input of t refers to a transaction of the batch with
+ *        tx_output_count <= input_index; bad_input[t] = the absolute index of the first such input
+ *     5. CV_RS_OK
+ *   first_bad[t], req_missing[r] (optional): as cv_notarise_batch.  bad_input[t]: 0xffffffff unless CV_RS_BAD_INPUT.
+ *   input_status[i]: 0 external, 1 in the batch and in range, 2 in the batch and out of range.
+ * graph[CV_RG_WORDS]:
+ *   CV_RG_STATUS     CV_RG_OK, CV_RG_BAD_ID or CV_RG_DUPLICATE_ID
+ *   CV_RG_WHICH      the smallest index of a transaction that is EMPTY / ID_MISMATCH, respectively the smallest index
+ *                    of a transaction whose id occurs more than once; 0xffffffff with CV_RG_OK
+ *   CV_RG_N_PASS     the leading transactions of order that pass everything this call checks (ntx: all of them)
+ *   CV_RG_STOP_CLASS, CV_RG_STOP_TX, CV_RG_STOP_INPUT   what stopped the walk: the outcome of the transaction it
+ *                    stopped at (with its bad_input), or CV_RS_UNRESOLVED / CV_RS_BAD_INPUT with the input met, going
+ *                    through the transaction's inputs in order (an unresolved input is met before an out-of-range
+ *                    one that comes later); 0xffffffff each when nothing stopped it
+ *   CV_RG_EXTERNAL   the number of inputs of status 0
+ *   CV_RG_MAXPROBE, CV_RG_WRAPS   diagnostics of the join table (longest probe, probes past its last slot)
+ *   With CV_RG_STATUS != CV_RG_OK, order is zero-filled, N_PASS is 0 and STOP_* are 0xffffffff; with several
+ *   transactions of one id, input_dep names the smallest index among them.
+ * seed: of the join table's hash (ids are hashes the serving peer can grind, so all eight words are mixed with it and
+ * no id bits choose a slot directly); 0 draws a fresh one, any other value makes a run reproducible.  The results
+ * but CV_RG_MAXPROBE / CV_RG_WRAPS do not depend on it.
+ * Synchronous, on one device (the least loaded); one upload, one read-back; order and the walk are computed on the
+ * host after it (a lexicographic depth-first order is sequential).  All before any device work: the range arrays
+ * (begin[0] == 0, monotone, the last entry the count) and child_begin's ends malformed, a leaf past
+ * leaf_arena[leaf_arena_bytes) or whose off + len wraps, or a missing array that a non-zero count needs: CV_E_ARGS;
+ * a count above 0xfffffffe, or more than 2^30 transactions or inputs: CV_E_TOO_LARGE; ntx == 0 returns CV_OK and
+ * touches nothing; ninputs == 0 is legal; a NULL context is checked last.  A probe that runs out of slots (it cannot):
+ * CV_E_HIP.  With CV_OPT_TIMELINE = 1 the call times its stages with HIP events (CV_STATS_RESOLVE).  Outputs as under
+ * Conventions. */
+#define CV_RS_OK                 0
+#define CV_RS_EMPTY              1  /* no leaves: MerkleTreeException out of stx.tx                          */
+#define CV_RS_ID_MISMATCH        2  /* recomputed id != claimed id: IllegalStateException                    */
+#define CV_RS_TX_INVALID         4  /* first bad signature is a SignatureException                           */
+#define CV_RS_BAD_KEY            5  /* first bad signature is an InvalidKeyException                         */
+#define CV_RS_SIGNATURES_MISSING 6  /* SignaturesMissingException (req_missing says which)                   */
+#define CV_RS_MALFORMED          7  /* a requirement is not a tree encoding (CV_VS_MALFORMED)                */
+#define CV_RS_BAD_INPUT          9  /* outputs[stateRef.index] out of range: IndexOutOfBoundsException       */
+#define CV_RS_UNRESOLVED        10  /* CV_RG_STOP_CLASS only: TransactionResolutionException                 */
+#define CV_RG_OK 0
+#define CV_RG_BAD_ID 1
+#define CV_RG_DUPLICATE_ID 2
+#define CV_RG_STATUS 0
+#define CV_RG_WHICH 1
+#define CV_RG_N_PASS 2
+#define CV_RG_STOP_CLASS 3
+#define CV_RG_STOP_TX 4
+#define CV_RG_STOP_INPUT 5
+#define CV_RG_EXTERNAL 6
+#define CV_RG_MAXPROBE 7
+#define CV_RG_WRAPS 8
+#define CV_RG_WORDS 9
+int cv_resolve_batch(cv_ctx *ctx, size_t ntx,
+    /* transactions and signatures, exactly as cv_notarise_batch (always validating) */
+    const uint8_t *leaf_arena, uint64_t leaf_arena_bytes, const uint64_t *leaf_off, const uint32_t *leaf_len,
+    const uint32_t *tx_leaf_begin /* ntx+1 */, const uint8_t *claimed_id /* ntx*32 */,
+    const uint8_t *pk /* nsig*32 */, const uint8_t *sig /* nsig*64 */, const uint32_t *tx_sig_begin /* ntx+1 */,
+    const uint8_t *sig_pre /* nsig, NULL = none */,
+    /* mustSign requirements, exactly the arrays of cv_missing_signers (no req_allowed) */
+    size_t nreq, size_t nnodes, size_t nchild, const uint8_t *kind, const uint8_t *leaf_key,
+    const int32_t *threshold, const uint32_t *child_begin, const uint32_t *child, const int32_t *weight,
+    const uint32_t *req_begin, const uint32_t *tx_req_begin, const uint8_t *sig_key,
+    /* the graph: the StateRefs of every transaction's inputs, in order, and its number of outputs */
+    size_t ninputs, const uint32_t *tx_input_begin /* ntx+1 */, const uint8_t *input_txhash /* ninputs*32 */,
+    const uint32_t *input_index /* ninputs */, const uint32_t *tx_output_count /* ntx */, uint64_t seed,
+    /* outputs */
+    uint8_t *outcome /* ntx */, uint32_t *first_bad /* ntx, optional */, uint8_t *req_missing /* nreq, optional */,
+    uint32_t *bad_input /* ntx */, uint32_t *input_dep /* ninputs */, uint8_t *input_status /* ninputs */,
+    uint32_t *order /* ntx */, uint32_t *graph /* CV_RG_WORDS */, uint8_t *ids /* ntx*32, optional */);
+
 /* ---------------------------------------------------------------- device-resident API
  * All pointers are device pointers on HIP device `device` (which must be in the context); work is
  * enqueued on `stream` (a hipStream_t, NULL = the context's stream for that device) and the call
@@ -785,11 +890,15 @@ int cv_get_option(cv_ctx *ctx, int option, int64_t *value);
  *                   the result copy (host-timed); first sub-chunk records; Merkle-group busy, verify-group busy, last
  *                   Merkle DMA end (ms; cv_verify_transactions); launch groups; host time from the call's entry to
  *                   its first input DMA enqueued (verify calls) and from the GPU work joined to the results in the
- *                   caller's arrays (ms); calls timed} */
+ *                   caller's arrays (ms); calls timed}
+ *   CV_STATS_RESOLVE {sums over the cv_resolve_batch calls timed with CV_OPT_TIMELINE = 1, in ms: upload, leaf hashes
+ *                   and trees, join (table clear, insert, probe), signature verify, missing signers, gate, read-back
+ *                   (HIP events around the stages), host order and walk (host-timed); calls timed} */
 #define CV_STATS_PIPE 0
 #define CV_STATS_SMALL 1
 #define CV_STATS_ROUTE 2
 #define CV_STATS_TIMELINE 3
+#define CV_STATS_RESOLVE 4
 int cv_diag_stats(cv_ctx *ctx, int which, double *out, size_t nout, int reset);
 
 /* max(msg_off[i] + msg_len[i]) over n records (0 for n = 0): the arena bytes a batch reaches, for the
