@@ -22,7 +22,7 @@ Error mapping (reference -> here):
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 
@@ -192,11 +192,7 @@ def verify_many(items: Sequence[VerifyItem], engine: Optional[native.Engine] = N
     m = len(idx)
     pk = np.empty((m, 32), np.uint8)
     sig = np.empty((m, 64), np.uint8)
-    lens = np.fromiter((len(items[i].content) for i in idx), dtype=np.uint32, count=m)
-    offs = np.zeros(m, np.uint64)
-    if m > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    arena = np.frombuffer(b"".join(items[i].content for i in idx) + b"\0" * 16, np.uint8)
+    arena, offs, lens = native.pack_blobs([items[i].content for i in idx])
     for j, i in enumerate(idx):
         pk[j] = np.frombuffer(items[i].key.encoded, np.uint8)
         sig[j] = np.frombuffer(items[i].sig_bits, np.uint8)
@@ -220,16 +216,6 @@ def verify_with_ecdsa(public_key: PublicKey, content: bytes, signature: OpaqueBy
 
 
 # ---------------------------------------------------------------- key pairs and signing
-def _pack_messages(msgs: Sequence[bytes]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """Messages back to back in one arena -> (arena, offsets, lengths)."""
-    m = len(msgs)
-    lens = np.fromiter((len(x) for x in msgs), np.uint32, count=m)
-    offs = np.zeros(m, np.uint64)
-    if m > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    return np.frombuffer(b"".join(msgs) + b"\0" * 16, np.uint8), offs, lens
-
-
 class KeyPair:
     """A java.security.KeyPair over Ed25519 as entropyToKeyPair / generateKeyPair build it
     (CryptoUtilities.kt:117-130): `public` is the EdDSAPublicKey, the private half is a native.Signer
@@ -256,7 +242,7 @@ class KeyPair:
         msgs = [bytes(x) for x in messages]
         if not msgs:
             return []
-        sigs = self._signer.sign(*_pack_messages(msgs))
+        sigs = self._signer.sign(*native.pack_blobs(msgs))
         return [DigitalSignature.WithKey(self.public, sigs[j].tobytes()) for j in range(len(msgs))]
 
     def sign_with_ecdsa(self, bytes_to_sign) -> DigitalSignature.WithKey:

@@ -296,6 +296,70 @@ def _check(rc: int, what: str):
         raise CvError(rc, what)
 
 
+# ---------------------------------------------------------------- marshalling (numpy alone: no library, no engine)
+def pack_blobs(blobs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Blobs back to back in one arena -> (arena u8, offsets u64, lengths u32).  The arena ends in 16 zero bytes, so
+    it is never empty."""
+    n = len(blobs)
+    lens = np.fromiter((len(b) for b in blobs), dtype=np.uint32, count=n)
+    offs = np.zeros(n, np.uint64)
+    if n > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    return np.frombuffer(b"".join(blobs) + b"\0" * 16, np.uint8), offs, lens
+
+
+def _arr(a, dt, n, what, width=1, exact=True):
+    """a flat, of dt, with n rows of width entries (exact=False: at least); never empty: `width` zeros stand for it."""
+    a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+    if a.size != n * width if exact else a.size < n * width:
+        raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
+    return a if a.size else np.zeros(width, dt)
+
+
+def _sig_args(sigs, ntx: int):
+    """sigs = (pk (nsig,32), sig (nsig,64), tx_sig_begin u32[ntx+1], sig_pre u8[nsig] or None) -> (the four as the
+    library takes them, nsig)."""
+    pk, sg, tsb, sig_pre = sigs
+    tsb = _arr(tsb, np.uint32, ntx + 1, "tx_sig_begin")
+    nsig = int(tsb[-1])
+    return [_arr(pk, np.uint8, nsig, "pk", 32), _arr(sg, np.uint8, nsig, "sig", 64), tsb,
+            None if sig_pre is None else _arr(sig_pre, np.uint8, nsig, "sig_pre")], nsig
+
+
+def _req_args(reqs, ntx: int, nsig: int, allowed: bool):
+    """reqs = (kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key), with
+    req_allowed or None behind them when `allowed` -> (the nine or ten as the library takes them, nreq, nnodes,
+    nchild)."""
+    kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key = reqs[:9]
+    tx_req_begin = _arr(tx_req_begin, np.uint32, ntx + 1, "tx_req_begin")
+    req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32).reshape(-1)
+    child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32).reshape(-1)
+    nreq, nnodes = req_begin.size - 1, child_begin.size - 1
+    child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
+    nchild = child.size
+    if nreq < 0 or nnodes < 0:
+        raise ValueError("the begin arrays must have count + 1 entries")
+    a = [_arr(kind, np.uint8, nnodes, "kind"), _arr(leaf_key, np.uint8, nnodes, "leaf_key", 32),
+         _arr(threshold, np.int32, nnodes, "threshold"), child_begin, child if nchild else np.zeros(1, np.uint32),
+         _arr(weight, np.int32, nchild, "weight"), req_begin, tx_req_begin, _arr(sig_key, np.uint8, nsig, "sig_key", 32)]
+    if allowed:
+        (req_allowed,) = reqs[9:]
+        a.append(None if req_allowed is None else _arr(req_allowed, np.uint8, nreq, "req_allowed"))
+    return a, nreq, nnodes, nchild
+
+
+def _outputs(names, fresh, out) -> list:
+    """The output arrays of a call in the order of names: the caller's from `out` (None: passed as NULL), else new
+    zeros of fresh[name] = (shape, dtype)."""
+    out = dict(out or {})
+    return [out[k] if k in out else np.zeros(*fresh[k]) for k in names]
+
+
+def _cut_outputs(names, arrays, rows: dict, default: int) -> dict:
+    """The outputs by name, each cut to its rows (rows[name], else default); None stays None."""
+    return {k: None if a is None else a[:rows.get(k, default)] for k, a in zip(names, arrays)}
+
+
 class Engine:
     """One context over a set of GPUs (bit d of device_mask = HIP device d; 0 = all).
 
@@ -658,6 +722,7 @@ class Engine:
         nn = _sz(0)
         rc = self._lib.cv_filtered_build(self._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len),
                                          _p(tx_leaf_begin), _p(keep), cap, *[_p(a) for a in out], ctypes.byref(nn))
+        # not _bounded_rc: here CV_E_ARGS also reports a nodes_cap that is too small, which _build_result words
         if rc == -3 and nn.value <= cap:
             self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
         return self._build_result(rc, "cv_filtered_build", ntx, cap, out, nn.value)
@@ -668,42 +733,24 @@ class Engine:
         """cv_missing_signers: the flat CompositeKey encoding of include/cordaverify.h (transactions.flatten_must_sign
         builds it) -> (req_missing u8[nreq]: 0 fulfilled, 1 missing, 2 malformed; tx_status u8[ntx]: CV_VS_*).
         req_allowed u8[nreq] and bitmap u64[ceil(nsig / 64)] are optional; wide_min forces a path (CK_WIDE_*)."""
-        def arr(a, dt, n, what, width=1):
-            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
-            if a.size != n * width:
-                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
-            return a if a.size else np.zeros(width, dt)
-        tx_req_begin = np.ascontiguousarray(tx_req_begin, dtype=np.uint32)
-        tx_sig_begin = np.ascontiguousarray(tx_sig_begin, dtype=np.uint32)
-        req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32)
-        child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32)
-        ntx, nreq, nnodes = tx_req_begin.size - 1, req_begin.size - 1, child_begin.size - 1
-        if ntx < 0 or nreq < 0 or nnodes < 0 or tx_sig_begin.size != ntx + 1:
+        tx_req_begin = np.ascontiguousarray(tx_req_begin, dtype=np.uint32).reshape(-1)
+        tx_sig_begin = np.ascontiguousarray(tx_sig_begin, dtype=np.uint32).reshape(-1)
+        ntx = tx_req_begin.size - 1
+        if ntx < 0 or tx_sig_begin.size != ntx + 1:
             raise ValueError("the begin arrays must have count + 1 entries")
-        kind = arr(kind, np.uint8, nnodes, "kind")
-        leaf_key = arr(leaf_key, np.uint8, nnodes, "leaf_key", 32)
-        threshold = arr(threshold, np.int32, nnodes, "threshold")
-        child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
-        nchild = child.size
-        weight = arr(weight, np.int32, nchild, "weight")
-        if nchild == 0:
-            child = np.zeros(1, np.uint32)
         sig_key = np.ascontiguousarray(sig_key, dtype=np.uint8).reshape(-1)
         if sig_key.size % 32:
             raise ValueError("sig_key must be rows of 32 bytes")
         nsig = sig_key.size // 32
-        if nsig == 0:
-            sig_key = np.zeros(32, np.uint8)
-        if req_allowed is not None:
-            req_allowed = arr(req_allowed, np.uint8, nreq, "req_allowed")
+        a_req, nreq, nnodes, nchild = _req_args((kind, leaf_key, threshold, child_begin, child, weight, req_begin,
+                                                 tx_req_begin, sig_key, req_allowed), ntx, nsig, allowed=True)
         if bitmap is not None:
-            bitmap = arr(bitmap, np.uint64, (nsig + 63) // 64, "bitmap")
+            bitmap = _arr(bitmap, np.uint64, (nsig + 63) // 64, "bitmap")
         req_missing = np.zeros(max(nreq, 1), np.uint8)
         tx_status = np.zeros(max(ntx, 1), np.uint8)
-        _check(self._lib.cv_missing_signers(self._h, ntx, nreq, nnodes, nchild, nsig, _p(kind), _p(leaf_key), _p(threshold),
-                                            _p(child_begin), _p(child), _p(weight), _p(req_begin), _p(tx_req_begin),
-                                            _p(sig_key), _p(tx_sig_begin), _p(req_allowed), _p(bitmap),
-                                            ctypes.c_uint32(wide_min), _p(req_missing), _p(tx_status)),
+        _check(self._lib.cv_missing_signers(self._h, ntx, nreq, nnodes, nchild, nsig, *[_p(a) for a in a_req[:9]],
+                                            _p(tx_sig_begin), _p(a_req[9]), _p(bitmap), ctypes.c_uint32(wide_min),
+                                            _p(req_missing), _p(tx_status)),
                "cv_missing_signers")
         return req_missing[:nreq], tx_status[:ntx]
 
@@ -721,17 +768,12 @@ class Engine:
         notary.  Returns a dict of NOTARISE_OUTPUTS (include/cordaverify.h).  out: arrays to write into by name; an
         optional output given as None is passed as NULL and comes back None.  CvError -4 when the set would pass its
         capacity: nothing changed and nothing written."""
-        def arr(a, dt, n, what, width=1):
-            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
-            if a.size != n * width:
-                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
-            return a if a.size else np.zeros(width, dt)
         ntx, arena, leaf_off, leaf_len, tx_leaf_begin = self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
-        tx_input_count = arr(tx_input_count, np.uint32, ntx, "tx_input_count")
-        claimed_id = arr(claimed_id, np.uint8, ntx, "claimed_id", 32)
-        caller = arr(caller, np.uint32, ntx, "caller")
+        tx_input_count = _arr(tx_input_count, np.uint32, ntx, "tx_input_count")
+        claimed_id = _arr(claimed_id, np.uint8, ntx, "claimed_id", 32)
+        caller = _arr(caller, np.uint32, ntx, "caller")
         if tx_pre is not None:
-            tx_pre = arr(tx_pre, np.uint8, ntx, "tx_pre")
+            tx_pre = _arr(tx_pre, np.uint8, ntx, "tx_pre")
         ns = int(tx_input_count[:ntx].sum())
         nreq = nnodes = nchild = 0
         a_sig = [None] * 4
@@ -739,42 +781,21 @@ class Engine:
         if sigs is not None:
             if reqs is None:
                 raise ValueError("a validating call needs the requirement arrays")
-            pk, sg, tsb, sig_pre = sigs
-            tsb = arr(tsb, np.uint32, ntx + 1, "tx_sig_begin")
-            nsig = int(tsb[-1])
-            kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key, req_allowed = reqs
-            tx_req_begin = arr(tx_req_begin, np.uint32, ntx + 1, "tx_req_begin")
-            req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32).reshape(-1)
-            child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32).reshape(-1)
-            nreq, nnodes = req_begin.size - 1, child_begin.size - 1
-            child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
-            nchild = child.size
-            if nreq < 0 or nnodes < 0:
-                raise ValueError("the begin arrays must have count + 1 entries")
-            a_sig = [arr(pk, np.uint8, nsig, "pk", 32), arr(sg, np.uint8, nsig, "sig", 64), tsb,
-                     None if sig_pre is None else arr(sig_pre, np.uint8, nsig, "sig_pre")]
-            a_req = [arr(kind, np.uint8, nnodes, "kind"), arr(leaf_key, np.uint8, nnodes, "leaf_key", 32),
-                     arr(threshold, np.int32, nnodes, "threshold"), child_begin,
-                     child if nchild else np.zeros(1, np.uint32), arr(weight, np.int32, nchild, "weight"), req_begin,
-                     tx_req_begin, arr(sig_key, np.uint8, nsig, "sig_key", 32),
-                     None if req_allowed is None else arr(req_allowed, np.uint8, nreq, "req_allowed")]
+            a_sig, nsig = _sig_args(sigs, ntx)
+            a_req, nreq, nnodes, nchild = _req_args(reqs, ntx, nsig, allowed=True)
         m, q = max(ns, 1), max(ntx, 1)
-        fresh = {"outcome": lambda: np.zeros(q, np.uint8), "ids": lambda: np.zeros((q, 32), np.uint8),
-                 "notary_sig": lambda: np.zeros((q, 64), np.uint8), "first_bad": lambda: np.zeros(q, np.uint32),
-                 "req_missing": lambda: np.zeros(max(nreq, 1), np.uint8), "state_conflict": lambda: np.zeros(m, np.uint8),
-                 "consumed_id": lambda: np.zeros((m, 32), np.uint8), "consumed_index": lambda: np.zeros(m, np.uint32),
-                 "consumed_caller": lambda: np.zeros(m, np.uint32)}
-        out = dict(out or {})
-        o = [out[k] if k in out else fresh[k]() for k in self.NOTARISE_OUTPUTS]
+        o = _outputs(self.NOTARISE_OUTPUTS,
+                     {"outcome": (q, np.uint8), "ids": ((q, 32), np.uint8), "notary_sig": ((q, 64), np.uint8),
+                      "first_bad": (q, np.uint32), "req_missing": (max(nreq, 1), np.uint8), "state_conflict": (m, np.uint8),
+                      "consumed_id": ((m, 32), np.uint8), "consumed_index": (m, np.uint32),
+                      "consumed_caller": (m, np.uint32)}, out)
         rc = self._lib.cv_notarise_batch(self._h, uniq._open(), signer._h, 1 if sigs is not None else 0, ntx, _p(arena),
                                          arena.size, _p(leaf_off), _p(leaf_len), _p(tx_leaf_begin), _p(tx_input_count),
                                          _p(claimed_id), _p(caller), _p(tx_pre), *[_p(a) for a in a_sig], nreq, nnodes,
                                          nchild, *[_p(a) for a in a_req], *[_p(a) for a in o])
-        if rc == -3:
-            self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
-        _check(rc, "cv_notarise_batch")
-        cut = {"outcome": ntx, "ids": ntx, "notary_sig": ntx, "first_bad": ntx, "req_missing": nreq}
-        return {k: None if a is None else a[:cut.get(k, ns)] for k, a in zip(self.NOTARISE_OUTPUTS, o)}
+        self._bounded_rc(rc, "cv_notarise_batch", (arena, leaf_off, leaf_len, tx_leaf_begin))
+        return _cut_outputs(self.NOTARISE_OUTPUTS, o,
+                            {"outcome": ntx, "ids": ntx, "notary_sig": ntx, "first_bad": ntx, "req_missing": nreq}, ns)
 
     def _tearoff_args(self, arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash, tree_begin, root):
         """The shared inputs of filtered_verify and tearoff_sign_batch as the library takes them."""
@@ -783,15 +804,11 @@ class Engine:
         if ntx < 0 or tree_begin.shape[0] != ntx + 1:
             raise ValueError("tx_leaf_begin and tree_begin must have ntx + 1 entries")
         nnodes = int(tree_begin[-1]) if ntx else 0
-
-        def arr(a, dt, n, what, width=1):
-            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
-            if a.size < n * width:
-                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
-            return a if a.size else np.zeros(width, dt)
-        nodes = [arr(kind, np.uint8, nnodes, "kind"), arr(left, np.uint32, nnodes, "left"),
-                 arr(right, np.uint32, nnodes, "right"), arr(node_hash, np.uint8, nnodes, "node_hash", 32)]
-        root = arr(root, np.uint8, ntx, "root", 32)
+        # exact=False: longer arrays pass, the ranges say what is read
+        nodes = [_arr(kind, np.uint8, nnodes, "kind", exact=False), _arr(left, np.uint32, nnodes, "left", exact=False),
+                 _arr(right, np.uint32, nnodes, "right", exact=False),
+                 _arr(node_hash, np.uint8, nnodes, "node_hash", 32, exact=False)]
+        root = _arr(root, np.uint8, ntx, "root", 32, exact=False)
         return ntx, nnodes, (arena, leaf_off, leaf_len, tx_leaf_begin), nodes, tree_begin, root
 
     def filtered_verify(self, arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash, tree_begin, root
@@ -804,9 +821,7 @@ class Engine:
         verdict, status = np.zeros(max(ntx, 1), np.uint8), np.zeros(max(ntx, 1), np.uint8)
         rc = self._lib.cv_filtered_verify(self._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len), _p(txb), nnodes,
                                           *[_p(a) for a in nodes], _p(tree_begin), _p(root), _p(verdict), _p(status))
-        if rc == -3:
-            self._merkle_args(arena, leaf_off, leaf_len, txb, scan=True)   # leaves past the arena: ValueError
-        _check(rc, "cv_filtered_verify")
+        self._bounded_rc(rc, "cv_filtered_verify", (arena, leaf_off, leaf_len, txb))
         return verdict[:ntx], status[:ntx]
 
     def tearoff_sign_batch(self, signer: "Signer", arena, leaf_off, leaf_len, tx_leaf_begin, kind, left, right, node_hash,
@@ -832,9 +847,7 @@ class Engine:
         rc = self._lib.cv_tearoff_sign_batch(self._h, signer._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len),
                                              _p(txb), nnodes, *[_p(a) for a in nodes], _p(tree_begin), _p(root),
                                              _p(leaf_pre), _p(outcome), _p(first_bad), _p(sig))
-        if rc == -3:
-            self._merkle_args(arena, leaf_off, leaf_len, txb, scan=True)   # leaves past the arena: ValueError
-        _check(rc, "cv_tearoff_sign_batch")
+        self._bounded_rc(rc, "cv_tearoff_sign_batch", (arena, leaf_off, leaf_len, txb))
         return outcome[:ntx], None if first_bad is None else first_bad[:ntx], sig[:ntx]
 
     RESOLVE_OUTPUTS = ("outcome", "first_bad", "req_missing", "bad_input", "input_dep", "input_status", "order", "graph",
@@ -851,53 +864,28 @@ class Engine:
         tx_output_count u32[ntx]; seed 0 draws a fresh one.  Returns a dict of RESOLVE_OUTPUTS
         (include/cordaverify.h; graph u32[9], see RG_WORDS).  out: arrays to write into by name; an optional output
         (first_bad, req_missing, ids) given as None is passed as NULL and comes back None."""
-        def arr(a, dt, n, what, width=1):
-            a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
-            if a.size != n * width:
-                raise ValueError(f"{what} must have {n * width} entries, not {a.size}")
-            return a if a.size else np.zeros(width, dt)
         ntx, arena, leaf_off, leaf_len, tx_leaf_begin = self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
         if ntx < 0:
             raise ValueError("tx_leaf_begin must have ntx + 1 entries")
-        claimed_id = arr(claimed_id, np.uint8, ntx, "claimed_id", 32)
-        pk, sg, tsb, sig_pre = sigs
-        tsb = arr(tsb, np.uint32, ntx + 1, "tx_sig_begin")
-        nsig = int(tsb[-1])
-        kind, leaf_key, threshold, child_begin, child, weight, req_begin, tx_req_begin, sig_key = reqs
-        tx_req_begin = arr(tx_req_begin, np.uint32, ntx + 1, "tx_req_begin")
-        req_begin = np.ascontiguousarray(req_begin, dtype=np.uint32).reshape(-1)
-        child_begin = np.ascontiguousarray(child_begin, dtype=np.uint32).reshape(-1)
-        nreq, nnodes = req_begin.size - 1, child_begin.size - 1
-        child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
-        nchild = child.size
-        if nreq < 0 or nnodes < 0:
-            raise ValueError("the begin arrays must have count + 1 entries")
-        a_sig = [arr(pk, np.uint8, nsig, "pk", 32), arr(sg, np.uint8, nsig, "sig", 64), tsb,
-                 None if sig_pre is None else arr(sig_pre, np.uint8, nsig, "sig_pre")]
-        a_req = [arr(kind, np.uint8, nnodes, "kind"), arr(leaf_key, np.uint8, nnodes, "leaf_key", 32),
-                 arr(threshold, np.int32, nnodes, "threshold"), child_begin, child if nchild else np.zeros(1, np.uint32),
-                 arr(weight, np.int32, nchild, "weight"), req_begin, tx_req_begin, arr(sig_key, np.uint8, nsig, "sig_key", 32)]
-        tib = arr(tx_input_begin, np.uint32, ntx + 1, "tx_input_begin")
+        claimed_id = _arr(claimed_id, np.uint8, ntx, "claimed_id", 32)
+        a_sig, nsig = _sig_args(sigs, ntx)
+        a_req, nreq, nnodes, nchild = _req_args(reqs, ntx, nsig, allowed=False)
+        tib = _arr(tx_input_begin, np.uint32, ntx + 1, "tx_input_begin")
         nin = int(tib[-1])
-        a_graph = [tib, arr(input_txhash, np.uint8, nin, "input_txhash", 32), arr(input_index, np.uint32, nin, "input_index"),
-                   arr(tx_output_count, np.uint32, ntx, "tx_output_count")]
+        a_graph = [tib, _arr(input_txhash, np.uint8, nin, "input_txhash", 32),
+                   _arr(input_index, np.uint32, nin, "input_index"), _arr(tx_output_count, np.uint32, ntx, "tx_output_count")]
         m, q = max(nin, 1), max(ntx, 1)
-        fresh = {"outcome": lambda: np.zeros(q, np.uint8), "first_bad": lambda: np.zeros(q, np.uint32),
-                 "req_missing": lambda: np.zeros(max(nreq, 1), np.uint8), "bad_input": lambda: np.zeros(q, np.uint32),
-                 "input_dep": lambda: np.zeros(m, np.uint32), "input_status": lambda: np.zeros(m, np.uint8),
-                 "order": lambda: np.zeros(q, np.uint32), "graph": lambda: np.zeros(len(RG_WORDS), np.uint32),
-                 "ids": lambda: np.zeros((q, 32), np.uint8)}
-        out = dict(out or {})
-        o = [out[k] if k in out else fresh[k]() for k in self.RESOLVE_OUTPUTS]
+        o = _outputs(self.RESOLVE_OUTPUTS,
+                     {"outcome": (q, np.uint8), "first_bad": (q, np.uint32), "req_missing": (max(nreq, 1), np.uint8),
+                      "bad_input": (q, np.uint32), "input_dep": (m, np.uint32), "input_status": (m, np.uint8),
+                      "order": (q, np.uint32), "graph": (len(RG_WORDS), np.uint32), "ids": ((q, 32), np.uint8)}, out)
         rc = self._lib.cv_resolve_batch(self._h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len), _p(tx_leaf_begin),
                                         _p(claimed_id), *[_p(a) for a in a_sig], nreq, nnodes, nchild,
                                         *[_p(a) for a in a_req], nin, *[_p(a) for a in a_graph], ctypes.c_uint64(seed),
                                         *[_p(a) for a in o])
-        if rc == -3:
-            self._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin, scan=True)   # leaves past the arena: ValueError
-        _check(rc, "cv_resolve_batch")
-        cut = {"req_missing": nreq, "input_dep": nin, "input_status": nin, "graph": len(RG_WORDS)}
-        return {k: None if a is None else a[:cut.get(k, ntx)] for k, a in zip(self.RESOLVE_OUTPUTS, o)}
+        self._bounded_rc(rc, "cv_resolve_batch", (arena, leaf_off, leaf_len, tx_leaf_begin))
+        return _cut_outputs(self.RESOLVE_OUTPUTS, o, {"req_missing": nreq, "input_dep": nin, "input_status": nin,
+                                                      "graph": len(RG_WORDS)}, ntx)
 
     # ------------------------------------------------------------ device-resident API
     def missing_signers_device(self, device: int, ntx: int, nreq: int, nnodes: int, nchild: int, nsig: int, d_kind: int,

@@ -42,7 +42,7 @@ from .crypto import (CompositeKey, DigitalSignature, EdDSAPublicKey, IllegalArgu
                      verify_with_ecdsa)
 from .transactions import (MerkleTreeException, SecureHash, SignaturesMissingException, SignedTransaction,
                            WireTransaction, _device_decidable, _missing_exception, compute_ids, flatten_must_sign,
-                           missing_signatures_batch)
+                           flatten_signatures, missing_signatures_batch, must_sign_reqs)
 
 
 # ---------------------------------------------------------------- timestamps (Structures.kt:412-423)
@@ -246,35 +246,16 @@ class BatchingNotary:
             leaves.extend(r.stx._wtx.leaves)
             txb.append(len(leaves))
             nin.append(len(r.stx._wtx.inputs))
-        lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
-        offs = np.zeros(len(leaves), np.uint64)
-        if len(leaves) > 1:
-            offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-        arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+        arena, offs, lens = native.pack_blobs(leaves)
         claimed = np.frombuffer(b"".join(r.stx.id.bytes for r in requests), np.uint8)
         tx_pre = np.array([1 if r.timestamp is not None and not self.timestamp_checker.is_valid(r.timestamp) else 0
                            for r in requests], np.uint8)
         sigs = reqs = None
         pre_err: Dict[int, Exception] = {}
         if self.validating:
-            pk, sg, sig_pre, tsb = [], [], [], [0]
-            zero32, zero64 = bytes(32), bytes(64)
-            for r in requests:
-                for s in r.stx.sigs:
-                    e = _prefilter(VerifyItem(s.by, r.stx.id.bytes, s.bits))
-                    if e is not None:
-                        pre_err[len(pk)] = e
-                    bad_key = isinstance(e, InvalidKeyException)
-                    pk.append(zero32 if bad_key else s.by.encoded)
-                    sg.append(zero64 if e is not None else bytes(s.bits))
-                    sig_pre.append(native.NS_PRE_KEY if bad_key else native.NS_PRE_SIGNATURE if e is not None else 0)
-                tsb.append(len(pk))
-            keys = np.frombuffer(b"".join(pk), np.uint8).reshape(-1, 32)
-            f = flatten_must_sign([r.stx for r in requests], (self.owning_key,))
-            sigs = (keys, np.frombuffer(b"".join(sg), np.uint8).reshape(-1, 64), np.array(tsb, np.uint32),
-                    np.array(sig_pre, np.uint8))
-            reqs = tuple(f[k] for k in ("kind", "leaf_key", "threshold", "child_begin", "child", "weight", "req_begin",
-                                        "tx_req_begin")) + (keys, f["req_allowed"])
+            stxs = [r.stx for r in requests]
+            sigs, keys, pre_err = flatten_signatures(stxs)
+            reqs = must_sign_reqs(flatten_must_sign(stxs, (self.owning_key,)), keys, allowed=True)
 
         def call(uniq, handles):
             out = self.engine.notarise_batch(uniq, self.key_pair._signer, arena, offs, lens, np.array(txb, np.uint32),

@@ -30,9 +30,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import native
-from .crypto import (IllegalStateException, InvalidKeyException, SignatureException, VerifyItem, _prefilter)
+from .crypto import IllegalStateException, InvalidKeyException, SignatureException
 from .transactions import (MerkleTreeException, SecureHash, SignedTransaction, _device_decidable, _missing_exception,
-                           compute_ids, flatten_must_sign, verify_signatures_batch)
+                           compute_ids, flatten_must_sign, flatten_signatures, must_sign_reqs, verify_signatures_batch)
 
 
 class TransactionResolutionException(Exception):
@@ -145,9 +145,6 @@ def flatten_resolve(stxs: Sequence[SignedTransaction]):
     absolute signature index)."""
     leaves: List[bytes] = []
     txb, tib, hashes, index, nout = [0], [0], [], [], []
-    pk, sg, sig_pre, tsb = [], [], [], [0]
-    pre_err: Dict[int, Exception] = {}
-    zero32, zero64 = bytes(32), bytes(64)
     for stx in stxs:
         w = stx._wtx
         leaves.extend(w.leaves)
@@ -157,28 +154,11 @@ def flatten_resolve(stxs: Sequence[SignedTransaction]):
             index.append(ref.index)
         tib.append(len(index))
         nout.append(len(w.outputs))
-        for s in stx.sigs:
-            e = _prefilter(VerifyItem(s.by, stx.id.bytes, s.bits))
-            if e is not None:
-                pre_err[len(pk)] = e
-            bad_key = isinstance(e, InvalidKeyException)
-            pk.append(zero32 if bad_key else s.by.encoded)
-            sg.append(zero64 if e is not None else bytes(s.bits))
-            sig_pre.append(native.NS_PRE_KEY if bad_key else native.NS_PRE_SIGNATURE if e is not None else 0)
-        tsb.append(len(pk))
-    lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
-    offs = np.zeros(len(leaves), np.uint64)
-    if len(leaves) > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    keys = np.frombuffer(b"".join(pk), np.uint8).reshape(-1, 32)
-    f = flatten_must_sign(stxs)
-    args = dict(arena=np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8), leaf_off=offs, leaf_len=lens,
-                tx_leaf_begin=np.array(txb, np.uint32),
+    arena, offs, lens = native.pack_blobs(leaves)
+    sigs, keys, pre_err = flatten_signatures(stxs)
+    args = dict(arena=arena, leaf_off=offs, leaf_len=lens, tx_leaf_begin=np.array(txb, np.uint32),
                 claimed_id=np.frombuffer(b"".join(s.id.bytes for s in stxs), np.uint8).reshape(-1, 32),
-                sigs=(keys, np.frombuffer(b"".join(sg), np.uint8).reshape(-1, 64), np.array(tsb, np.uint32),
-                      np.array(sig_pre, np.uint8)),
-                reqs=tuple(f[k] for k in ("kind", "leaf_key", "threshold", "child_begin", "child", "weight", "req_begin",
-                                          "tx_req_begin")) + (keys,),
+                sigs=sigs, reqs=must_sign_reqs(flatten_must_sign(stxs), keys, allowed=False),
                 tx_input_begin=np.array(tib, np.uint32),
                 input_txhash=np.frombuffer(b"".join(hashes), np.uint8).reshape(-1, 32),
                 input_index=np.array(index, np.uint32), tx_output_count=np.array(nout, np.uint32))

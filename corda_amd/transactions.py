@@ -19,7 +19,7 @@ import numpy as np
 
 from . import native
 from .crypto import (CompositeKey, DigitalSignature, EdDSAPublicKey, IllegalArgumentException, IllegalStateException,
-                     SignatureException, VerifyItem, verify_many)
+                     InvalidKeyException, SignatureException, VerifyItem, _prefilter, verify_many)
 
 
 class MerkleTreeException(Exception):
@@ -91,11 +91,7 @@ def compute_ids(txs: Sequence[WireTransaction], engine: Optional[native.Engine] 
     for t in txs:
         leaves.extend(t.leaves)
         begin.append(len(leaves))
-    lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
-    offs = np.zeros(len(leaves), np.uint64)
-    if len(leaves) > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+    arena, offs, lens = native.pack_blobs(leaves)
     eng = engine or native.default_engine()
     ids, st = eng.merkle_tx_ids(arena, offs, lens, np.array(begin, np.uint32))
     out = []
@@ -244,6 +240,38 @@ def flatten_must_sign(stxs: Sequence[SignedTransaction], allowed: Iterable[Compo
             "req_allowed": np.array(req_allowed, np.uint8)}
 
 
+def must_sign_reqs(f: Dict[str, np.ndarray], keys: np.ndarray, allowed: bool) -> tuple:
+    """flatten_must_sign's dict as the `reqs` of Engine.notarise_batch (allowed: req_allowed last) or resolve_batch;
+    keys: the signers' keys row by row with the signatures (flatten_signatures), not the dict's EdDSA-only sig_key."""
+    reqs = tuple(f[k] for k in ("kind", "leaf_key", "threshold", "child_begin", "child", "weight", "req_begin",
+                                "tx_req_begin")) + (keys,)
+    return reqs + (f["req_allowed"],) if allowed else reqs
+
+
+def flatten_signatures(stxs: Sequence[SignedTransaction]):
+    """Every signature of stxs through the host prefilter (non-EdDSA keys, bad lengths) -> (the `sigs` of
+    Engine.notarise_batch / resolve_batch: (pk, sig, tx_sig_begin, sig_pre), keys = pk, pre_err: the prefilter's
+    exception by absolute signature index).  A signature that fails comes with zero bytes and its NS_PRE_* code, a
+    key that fails with zero bytes too."""
+    pk, sg, sig_pre, tsb = [], [], [], [0]
+    pre_err: Dict[int, Exception] = {}
+    zero32, zero64 = bytes(32), bytes(64)
+    for stx in stxs:
+        for s in stx.sigs:
+            e = _prefilter(VerifyItem(s.by, stx.id.bytes, s.bits))
+            if e is not None:
+                pre_err[len(pk)] = e
+            bad_key = isinstance(e, InvalidKeyException)
+            pk.append(zero32 if bad_key else s.by.encoded)
+            sg.append(zero64 if e is not None else bytes(s.bits))
+            sig_pre.append(native.NS_PRE_KEY if bad_key else native.NS_PRE_SIGNATURE if e is not None else 0)
+        tsb.append(len(pk))
+    keys = np.frombuffer(b"".join(pk), np.uint8).reshape(-1, 32)
+    sigs = (keys, np.frombuffer(b"".join(sg), np.uint8).reshape(-1, 64), np.array(tsb, np.uint32),
+            np.array(sig_pre, np.uint8))
+    return sigs, keys, pre_err
+
+
 def _missing_exception(stx: SignedTransaction, needed) -> Optional[SignaturesMissingException]:
     """The SignaturesMissingException of _finish_verify for the needed (missing and not allowed) entries."""
     if not needed:
@@ -379,11 +407,7 @@ def verify_signatures_batch_fused(stxs: Sequence[SignedTransaction], allowed_to_
                 pk.append(s.by.encoded)
                 sig.append(s.bits)
             sbegin.append(len(pk))
-        lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
-        offs = np.zeros(len(leaves), np.uint64)
-        if len(leaves) > 1:
-            offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-        arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+        arena, offs, lens = native.pack_blobs(leaves)
         pk_a = np.frombuffer(b"".join(pk), np.uint8).reshape(-1, 32)
         sig_a = np.frombuffer(b"".join(sig), np.uint8).reshape(-1, 64)
         ok, ids, _, _ = eng.verify_transactions(arena, offs, lens, np.array(lbegin, np.uint32), pk_a, sig_a,
@@ -672,11 +696,7 @@ def flatten_filtered(items, classify=None):
         kind += k; left += l; right += r; hashes += h
         tb.append(len(kind))
         roots.append(root.bytes)
-    lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
-    offs = np.zeros(len(leaves), np.uint64)
-    if len(leaves) > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+    arena, offs, lens = native.pack_blobs(leaves)
     return (arena, offs, lens, np.array(lb, np.uint32), np.array(kind, np.uint8), np.array(left, np.uint32),
             np.array(right, np.uint32), np.frombuffer(b"".join(hashes), np.uint8).reshape(-1, 32),
             np.array(tb, np.uint32), np.frombuffer(b"".join(roots), np.uint8).reshape(-1, 32),
@@ -722,11 +742,7 @@ def build_filtered_batch(wtxs: Sequence[WireTransaction], filters, engine: Optio
             leaves.extend(group)
             keep.extend(1 if f(x) else 0 for x in group)
         begin.append(len(leaves))
-    lens = np.fromiter((len(b) for b in leaves), dtype=np.uint32, count=len(leaves))
-    offs = np.zeros(len(leaves), np.uint64)
-    if len(leaves) > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    arena = np.frombuffer(b"".join(leaves) + b"\0" * 16, np.uint8)
+    arena, offs, lens = native.pack_blobs(leaves)
     eng = engine or native.default_engine()
     out = eng.filtered_build(arena, offs, lens, np.array(begin, np.uint32), np.array(keep, np.uint8))
     ids: List[Optional[SecureHash]] = []

@@ -37,6 +37,39 @@ def test_every_case_equals_the_reference(engine, corpus, n):
     assert ran >= 5                                    # chain, reversed chain, outside only, no inputs, self-reference
 
 
+def _nothing_to_check(engine, corpus):
+    """One transaction with leaves and nothing else: N = nreq = nnodes = nchild = ninputs = 0."""
+    b = C.real(engine, corpus, [C.spec()])
+    none, u32 = np.zeros((0, 32), np.uint8), lambda *a: np.array(a, np.uint32)
+    b["sigs"] = (none, np.zeros((0, 64), np.uint8), u32(0, 0), None)
+    b["reqs"] = (np.zeros(0, np.uint8), none, np.zeros(0, np.int32), u32(0), u32(), np.zeros(0, np.int32), u32(0), u32(0, 0),
+                 none)
+    return b
+
+
+def _one_signature_each(engine, corpus):
+    """65 transactions with one signature each, the one their requirement names: the verdict bitmap crosses a word."""
+    b = C.real(engine, corpus, C.chain(65))
+    pk, sig, _, _ = b["sigs"]
+    b["sigs"] = (pk[1::2].copy(), sig[1::2].copy(), np.arange(66, dtype=np.uint32), None)
+    b["reqs"] = b["reqs"][:8] + (pk[1::2].copy(),)
+    return b
+
+
+@pytest.mark.parametrize("build, outcome", ((_nothing_to_check, native.CV_RS_TX_INVALID),
+                                            (_one_signature_each, native.CV_RS_OK)))
+def test_empty_pieces_equal_the_reference(engine, corpus, build, outcome):
+    """Pieces of the call's one buffer at zero bytes, and one signature a transaction (a transaction without leaves is
+    C.CASES["empty_mid_chain"], one without inputs "no_inputs", both in test_every_case_equals_the_reference).  A
+    transaction without signatures is invalid (the reference's "no_signatures" case); the others pass."""
+    b = build(engine, corpus)
+    txs, ids, req_missing = C.components(engine, b)
+    got = engine.resolve_batch(**b, seed=3)
+    C.same(got, C.resolve_ref(txs), build.__name__)
+    assert np.array_equal(got["ids"], ids) and np.array_equal(got["req_missing"], req_missing)
+    assert (got["outcome"] == outcome).all()
+
+
 def test_optional_outputs_and_fresh_seed(engine, corpus):
     """seed 0 draws one; the optional outputs may be left out."""
     b = C.real(engine, corpus, C.CASES["diamond"](65))
