@@ -446,6 +446,66 @@ static int key_resolve(Device &d, uint32_t cap, size_t nk, const uint8_t *keys, 
     return CV_OK;
 }
 
+// cv_host.h: the keyed verify behind cv_ed25519_verify_device_keyed and the fused batch calls
+int cvh::verify_keyed_locked(cv_ctx *ctx, Device &d, size_t n, size_t nkeys, const uint8_t *hkeys, const uint8_t *d_keys,
+                             const uint32_t *d_key_index, const uint8_t *d_sig, const uint8_t *d_arena,
+                             const uint64_t *d_off, const uint32_t *d_len, uint64_t *d_bitmap, uint8_t *d_status,
+                             hipStream_t s, float *phase_ms) {
+    const Opts o = ctx->opts();
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    if (phase_ms)
+        for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
+    Slot &sl = pick_slot(d, s);
+    if (e == hipSuccess) e = ensure_verify_ws(sl, n);
+    if (e == hipSuccess && phase_ms) e = hipEventRecord(ev[0], s);
+    if (e == hipSuccess) e = ws_begin(d, sl, s);
+    if (e == hipSuccess) e = pool_begin(d.kc, s);
+    // device-API keyed calls also wait for the pool's previous user on another stream (their streams are the
+    // caller's: an epoch reset can only wait for the last of them, so they stay a chain)
+    if (e == hipSuccess && d.kc.last && d.kc.last != s) e = hipStreamWaitEvent(s, d.kc.ev, 0);
+    std::vector<uint32_t> sok;
+    bool prepared = false;
+    int rc = e == hipSuccess ? key_resolve(d, ctx->key_cap.load(), nkeys, hkeys, nullptr, sok, s, &prepared) : hip_rc(e);
+    KeyCache &kc = d.kc;
+    // a slot_of_key that grows is freed: the previous keyed call still queued on the pool reads it
+    if (rc == CV_OK && nkeys * 4 > kc.slot_of_key.cap) rc = hip_rc(pool_quiesce(d));
+    if (rc == CV_OK) rc = hip_rc(kc.slot_of_key.ensure(nkeys * 4));
+    // slot_of_key goes up through the pool's pinned staging, which the previous keyed call's upload may
+    // still be reading: that call's pool event (after its verify) has passed once its upload has
+    if (rc == CV_OK && kc.pin_busy) rc = hip_rc(hipEventSynchronize(kc.pin_ev));
+    if (rc == CV_OK) rc = hip_rc(kc.pin.ensure(nkeys * 4));
+    if (rc == CV_OK) {
+        std::memcpy(kc.pin.p, sok.data(), nkeys * 4);
+        rc = hip_rc(hipMemcpyAsync(kc.slot_of_key.p, kc.pin.p, nkeys * 4, hipMemcpyHostToDevice, s));
+    }
+    if (rc == CV_OK && !kc.pin_ev) rc = hip_rc(hipEventCreateWithFlags(&kc.pin_ev, hipEventDisableTiming));
+    if (rc == CV_OK) rc = hip_rc(hipEventRecord(kc.pin_ev, s));
+    kc.pin_busy = rc == CV_OK;
+    if (rc == CV_OK)
+        rc = hip_rc(cvk_verify_keyed(&o.plan, (uint32_t)n, d_keys, d_key_index, kc.slot_of_key.as<uint32_t>(),
+                                     kc.ktab.as<uint32_t>(), kc.kok.as<uint8_t>(), d_sig, d_arena, d_off, d_len, d_bitmap,
+                                     d_status, sl.ws_hs.as<uint32_t>(), sl.ws_R.as<uint32_t>(), sl.ws_ok.as<uint8_t>(),
+                                     sl.ws_cap, s, phase_ms ? ev + 1 : nullptr));
+    if (sl.ev) {
+        const hipError_t e2 = ws_end(sl, s);
+        if (rc == CV_OK) rc = hip_rc(e2);
+    }
+    if (d.kc.ev) {
+        const hipError_t e2 = pool_end(d.kc, s);
+        if (rc == CV_OK) rc = hip_rc(e2);
+    }
+    if (rc != CV_OK) (void)hipStreamSynchronize(s);   // error paths: nothing queued outlives the call
+    if (rc == CV_OK && phase_ms) {
+        e = hipEventSynchronize(ev[4]);
+        for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
+        rc = hip_rc(e);
+    }
+    for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    return rc;
+}
+
 // ---------------------------------------------------------------- verify (host buffers): small paths
 // The caller's record arrays of one host-buffer call.  Keyed calls carry keys[nkeys][32] + key_index[n]
 // instead of per-record keys.
@@ -2189,7 +2249,6 @@ int cv_ed25519_verify_device_keyed(cv_ctx *ctx, int device, size_t n, size_t nke
     Device *d = find_dev(ctx, device);
     if (!d || nkeys == 0 || !d_keys || !d_key_index || !d_sig || !d_arena || !d_off || !d_len || !d_bitmap)
         return CV_E_ARGS;
-    const Opts o = ctx->opts();
     std::lock_guard<std::mutex> g(d->mu);
     CV_TRY(hipSetDevice(d->ordinal));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : d->stream;
@@ -2197,61 +2256,11 @@ int cv_ed25519_verify_device_keyed(cv_ctx *ctx, int device, size_t n, size_t nke
     std::vector<uint8_t> hkeys(nkeys * 32);
     CV_TRY(hipMemcpyAsync(hkeys.data(), d_keys, nkeys * 32, hipMemcpyDeviceToHost, s));
     CV_TRY(hipStreamSynchronize(s));
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    if (phase_ms)
-        for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipEventCreate(&ev[k]);
-    Slot &sl = pick_slot(*d, s);
-    if (e == hipSuccess) e = ensure_verify_ws(sl, n);
-    if (e == hipSuccess && phase_ms) e = hipEventRecord(ev[0], s);
-    if (e == hipSuccess) e = ws_begin(*d, sl, s);
-    if (e == hipSuccess) e = pool_begin(d->kc, s);
-    // device-API keyed calls also wait for the pool's previous user on another stream (their streams are the
-    // caller's: an epoch reset can only wait for the last of them, so they stay a chain)
-    if (e == hipSuccess && d->kc.last && d->kc.last != s) e = hipStreamWaitEvent(s, d->kc.ev, 0);
-    std::vector<uint32_t> sok;
-    bool prepared = false;
-    int rc = e == hipSuccess ? key_resolve(*d, ctx->key_cap.load(), nkeys, hkeys.data(), nullptr, sok, s, &prepared) : hip_rc(e);
-    KeyCache &kc = d->kc;
-    // a slot_of_key that grows is freed: the previous keyed call still queued on the pool reads it
-    if (rc == CV_OK && nkeys * 4 > kc.slot_of_key.cap) rc = hip_rc(pool_quiesce(*d));
-    if (rc == CV_OK) rc = hip_rc(kc.slot_of_key.ensure(nkeys * 4));
-    // slot_of_key goes up through the pool's pinned staging, which the previous keyed call's upload may
-    // still be reading: that call's pool event (after its verify) has passed once its upload has
-    if (rc == CV_OK && kc.pin_busy) rc = hip_rc(hipEventSynchronize(kc.pin_ev));
-    if (rc == CV_OK) rc = hip_rc(kc.pin.ensure(nkeys * 4));
-    if (rc == CV_OK) {
-        std::memcpy(kc.pin.p, sok.data(), nkeys * 4);
-        rc = hip_rc(hipMemcpyAsync(kc.slot_of_key.p, kc.pin.p, nkeys * 4, hipMemcpyHostToDevice, s));
-    }
-    if (rc == CV_OK && !kc.pin_ev) rc = hip_rc(hipEventCreateWithFlags(&kc.pin_ev, hipEventDisableTiming));
-    if (rc == CV_OK) rc = hip_rc(hipEventRecord(kc.pin_ev, s));
-    kc.pin_busy = rc == CV_OK;
-    if (rc == CV_OK)
-        rc = hip_rc(cvk_verify_keyed(&o.plan, (uint32_t)n, static_cast<const uint8_t *>(d_keys),
-                                     static_cast<const uint32_t *>(d_key_index), kc.slot_of_key.as<uint32_t>(),
-                                     kc.ktab.as<uint32_t>(), kc.kok.as<uint8_t>(), static_cast<const uint8_t *>(d_sig),
-                                     static_cast<const uint8_t *>(d_arena), static_cast<const uint64_t *>(d_off),
-                                     static_cast<const uint32_t *>(d_len), static_cast<uint64_t *>(d_bitmap),
-                                     static_cast<uint8_t *>(d_status), sl.ws_hs.as<uint32_t>(), sl.ws_R.as<uint32_t>(),
-                                     sl.ws_ok.as<uint8_t>(), sl.ws_cap, s, phase_ms ? ev + 1 : nullptr));
-    if (sl.ev) {
-        const hipError_t e2 = ws_end(sl, s);
-        if (rc == CV_OK) rc = hip_rc(e2);
-    }
-    if (d->kc.ev) {
-        const hipError_t e2 = pool_end(d->kc, s);
-        if (rc == CV_OK) rc = hip_rc(e2);
-    }
-    if (rc != CV_OK) (void)hipStreamSynchronize(s);   // error paths: nothing queued outlives the call
-    if (rc == CV_OK && phase_ms) {
-        e = hipEventSynchronize(ev[4]);
-        for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
-        rc = hip_rc(e);
-    }
-    for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    return rc;
+    return verify_keyed_locked(ctx, *d, n, nkeys, hkeys.data(), static_cast<const uint8_t *>(d_keys),
+                               static_cast<const uint32_t *>(d_key_index), static_cast<const uint8_t *>(d_sig),
+                               static_cast<const uint8_t *>(d_arena), static_cast<const uint64_t *>(d_off),
+                               static_cast<const uint32_t *>(d_len), static_cast<uint64_t *>(d_bitmap),
+                               static_cast<uint8_t *>(d_status), s, phase_ms);
 }
 
 int cv_merkle_tx_ids_device(cv_ctx *ctx, int device, size_t ntx, size_t nleaves, const void *d_arena,

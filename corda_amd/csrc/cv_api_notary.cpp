@@ -91,12 +91,14 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
     const size_t w_own = lay.take(4 * S), w_last = lay.take(4 * S), w_s0 = lay.take(4 * T), w_s1 = lay.take(4 * T);
     const size_t w_ust = lay.take(T), w_list = lay.take(4 * T), w_soff = lay.take(8 * T), w_slen = lay.take(4 * T);
     const size_t w_csig = lay.take(64 * T);
+    FusedKeyed fk;                                           // CV_OPT_FUSED_KEYED: no pieces unless the call dedupes
+    fk.plan(ctx->opts(), ctx->key_cap.load(), N, lay);
     const size_t o_out = lay.take(T), o_ids = lay.take(32 * T), o_fb = lay.take(4 * T), o_miss = lay.take(R);
     const size_t o_sc = lay.take(S), o_cid = lay.take(32 * S), o_cix = lay.take(4 * S), o_cc = lay.take(4 * S);
     const size_t o_nsig = lay.take(64 * T);
     const size_t out_bytes = lay.top - o_out, total = lay.top + 16;
     CV_TRY(u->nin.ensure(in_bytes + 16));
-    CV_TRY(u->nout.ensure(out_bytes + 16));
+    CV_TRY(u->nout.ensure(std::max(out_bytes, fk.pinned_bytes()) + 16));
     CV_TRY(u->nws.ensure(total));
 
     // pack: the leaf offsets rebased to the copied part of the arena; the states' prefix sum and leaf indices
@@ -146,6 +148,8 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
     int rc = uniq_stat_begin(u);
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(base, h, in_bytes, hipMemcpyHostToDevice, s));
+    // the key dedupe ahead of the Merkle kernels; its count and keys come back through the outputs' pinned block
+    CV_TRY(fk.enqueue(base, base + i_pk, key_seed(1) | 1, u->nout.p, s));
 
     uint32_t *const d_llen = at<uint32_t>(base, i_llen), *const d_txb = at<uint32_t>(base, i_txb);
     uint32_t *const d_tsb = at<uint32_t>(base, i_tsb), *const d_ldig = at<uint32_t>(base, w_ldig);
@@ -169,8 +173,19 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
         if (N) {
             CV_TRY(cvk_tx_sig_refs((uint32_t)N, 0, (uint32_t)T, 0, d_tsb, at<uint64_t>(base, w_voff),
                                    at<uint32_t>(base, w_vlen), s));
-            rc = cv_ed25519_verify_device(ctx, u->ordinal, N, base + i_pk, base + i_sig, base + o_ids, base + w_voff,
-                                          base + w_vlen, base + w_bm, base + w_sst, s);
+            size_t nkeys = 0;
+            rc = fk.decide(u->nout.p, &nkeys);
+            if (rc != CV_OK) return rc;
+            if (nkeys) {
+                // the key pool is the device's: its lock inside the set's, as the unkeyed call below takes it
+                Device &d = *find_dev(ctx, u->ordinal);
+                std::lock_guard<std::mutex> gd(d.mu);
+                rc = verify_keyed_locked(ctx, d, N, nkeys, fk.host_keys(u->nout.p), base + fk.keys,
+                                         at<uint32_t>(base, fk.kidx), base + i_sig, base + o_ids, at<uint64_t>(base, w_voff),
+                                         at<uint32_t>(base, w_vlen), d_bm, base + w_sst, s, nullptr);
+            } else
+                rc = cv_ed25519_verify_device(ctx, u->ordinal, N, base + i_pk, base + i_sig, base + o_ids, base + w_voff,
+                                              base + w_vlen, base + w_bm, base + w_sst, s);
             if (rc != CV_OK) return rc;
         }
         const CvCk a = ck_args(base, {T, R, nnodes, nchild, N},

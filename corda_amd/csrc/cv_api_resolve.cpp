@@ -91,7 +91,8 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_
         std::random_device rd;
         seed = (key_seed(0) ^ (((uint64_t)rd() << 32) | rd())) | 1;
     }
-    const bool timed = ctx->opts().timeline != 0;
+    const Opts opts = ctx->opts();
+    const bool timed = opts.timeline != 0;
 
     return dispatch_one(ctx, T, [&](Device &d, size_t, size_t, int threads) {
         CV_TRY(hipSetDevice(d.ordinal));
@@ -108,13 +109,15 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_
         const size_t i_cnt = lay.take(4 * T), in_bytes = lay.top;
         const size_t w_ldig = lay.take(32 * L), w_mst = lay.take(T), w_voff = lay.take(8 * N), w_vlen = lay.take(4 * N);
         const size_t w_bm = lay.take(8 * W), w_sst = lay.take(N), w_ck = lay.take((size_t)cvck_ws_bytes(T, nnodes));
+        FusedKeyed fk;                                       // CV_OPT_FUSED_KEYED: no pieces unless the call dedupes
+        fk.plan(opts, ctx->key_cap.load(), N, lay);
         const size_t w_ckst = lay.take(T), w_tab = lay.take(4 * slots);
         const size_t o_stat = lay.take(4 * CVR_D_WORDS), o_out = lay.take(T), o_fb = lay.take(4 * T), o_miss = lay.take(R);
         const size_t o_bin = lay.take(4 * T), o_dep = lay.take(4 * I), o_ist = lay.take(I), o_ids = lay.take(32 * T);
         const size_t out_bytes = lay.top - o_stat, total = lay.top + 16;
         static_assert(CVR_D_ERROR == 4 && CVR_D_WORDS == 8, "the counters' two halves are cleared by one memset each");
         CV_TRY(d.ts_in.ensure(in_bytes + 16));
-        CV_TRY(d.ts_out.ensure(out_bytes + 16));
+        CV_TRY(d.ts_out.ensure(std::max(out_bytes, fk.pinned_bytes()) + 16));
         CV_TRY(d.pmt.ensure(total));
 
         // pack: the leaf offsets rebased to the copied part of the arena
@@ -153,6 +156,8 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_
         CV_TRY(clk.mark(0, s));
         CV_TRY(hipMemcpyAsync(base, h, in_bytes, hipMemcpyHostToDevice, s));
         CV_TRY(clk.mark(1, s));
+        // the key dedupe ahead of the Merkle kernels; its count and keys come back through the outputs' pinned block
+        CV_TRY(fk.enqueue(base, base + i_pk, seed, d.ts_out.p, s));
 
         uint32_t *const d_llen = at<uint32_t>(base, i_llen), *const d_txb = at<uint32_t>(base, i_txb);
         uint32_t *const d_tsb = at<uint32_t>(base, i_tsb), *const d_ldig = at<uint32_t>(base, w_ldig);
@@ -179,8 +184,17 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_
         if (N) {
             CV_TRY(cvk_tx_sig_refs((uint32_t)N, 0, (uint32_t)T, 0, d_tsb, at<uint64_t>(base, w_voff),
                                    at<uint32_t>(base, w_vlen), s));
-            CV_TRY(verify_device_locked(ctx, d, N, base + i_pk, base + i_sig, base + o_ids, at<uint64_t>(base, w_voff),
-                                        at<uint32_t>(base, w_vlen), at<uint64_t>(base, w_bm), base + w_sst, s));
+            size_t nkeys = 0;
+            int rc = fk.decide(d.ts_out.p, &nkeys);
+            if (rc != CV_OK) return rc;
+            if (nkeys) {
+                rc = verify_keyed_locked(ctx, d, N, nkeys, fk.host_keys(d.ts_out.p), base + fk.keys,
+                                         at<uint32_t>(base, fk.kidx), base + i_sig, base + o_ids, at<uint64_t>(base, w_voff),
+                                         at<uint32_t>(base, w_vlen), at<uint64_t>(base, w_bm), base + w_sst, s, nullptr);
+                if (rc != CV_OK) return rc;
+            } else
+                CV_TRY(verify_device_locked(ctx, d, N, base + i_pk, base + i_sig, base + o_ids, at<uint64_t>(base, w_voff),
+                                            at<uint32_t>(base, w_vlen), at<uint64_t>(base, w_bm), base + w_sst, s));
         }
         CV_TRY(clk.mark(4, s));
         const CvCk a = ck_args(base, {T, R, nnodes, nchild, N},

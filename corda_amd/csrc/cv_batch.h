@@ -88,6 +88,57 @@ template <class F> inline int dispatch_one(cv_ctx *ctx, size_t n, F fn) {
     return dispatch(ctx, o, n, 1, fn);
 }
 
+// ---------------------------------------------------------------- the keyed route of the fused calls
+// CV_OPT_FUSED_KEYED for cv_notarise_batch and cv_resolve_batch, in the order a call uses it:
+//   plan     whether the call dedupes its n signatures' keys at all — mode 2, or mode 1 with n above the tri-chain size
+//            (below it the rule keeps the unkeyed path whatever the keys) — the most key rows it would read back
+//            (floor(n / 8) under mode 1, n under mode 2, the pool's capacity under both) and its pieces of the call's
+//            device buffer: head (the count) | keys, read back as one piece, | key_index | the dedupe's workspace
+//   enqueue  right after the upload: the dedupe (it needs the keys alone, so it runs ahead of the Merkle kernels), the
+//            copy of head and rows into the call's pinned block, an event behind it
+//   decide   before the verify: waits for the event — the one synchronisation the route adds; the kernels enqueued
+//            since run meanwhile — and gives the distinct keys when the call takes the keyed path, 0 when it stays
+//            unkeyed (more keys than rows), CV_E_HIP after a probe error
+struct FusedKeyed {
+    bool want = false;
+    size_t n = 0, rows = 0, head = 0, keys = 0, kidx = 0, ws = 0;
+    CvdLayout L{};
+    hipEvent_t ev = nullptr;
+    ~FusedKeyed() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    void plan(const Opts &o, uint32_t key_cap, size_t nsig, Layout &lay) {
+        n = nsig;
+        rows = std::min<size_t>(o.fused_keyed == 2 ? n : n / 8, key_cap);
+        want = rows != 0 && (o.fused_keyed == 2 || (o.fused_keyed == 1 && n > o.plan.tri_max));
+        if (!want) return;
+        L = cvd_layout(n);
+        head = lay.take(16), keys = lay.take(32 * n), kidx = lay.take(4 * n), ws = lay.take((size_t)L.bytes);
+    }
+    size_t pinned_bytes() const { return want ? 16 + 32 * rows : 0; }
+    hipError_t enqueue(uint8_t *base, const uint8_t *d_pk, uint64_t seed, void *pin, hipStream_t s) {
+        if (!want) return hipSuccess;
+        const CvDedupe D = cvd_args(n, d_pk, base + keys, base + kidx, base + head, base + ws, seed, L);
+        uint32_t *sums[CVD_LEVELS];
+        for (int k = 0; k < CVD_LEVELS; k++) sums[k] = at<uint32_t>(base, ws + (size_t)L.sum[k]);
+        hipError_t e = cvk_dedupe(&D, sums, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(pin, base + head, pinned_bytes(), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ev, s);
+        return e;
+    }
+    int decide(const void *pin, size_t *nkeys) const {
+        *nkeys = 0;
+        if (!want) return CV_OK;
+        CV_TRY(hipEventSynchronize(ev));
+        const uint32_t nk = *static_cast<const uint32_t *>(pin);
+        if (nk == 0 || nk > n) return CV_E_HIP;
+        if (nk <= rows) *nkeys = nk;
+        return CV_OK;
+    }
+    const uint8_t *host_keys(const void *pin) const { return static_cast<const uint8_t *>(pin) + 16; }
+};
+
 // ---------------------------------------------------------------- missing signers
 // CvCk over one buffer: the counts and the offsets of its arrays, in CvCk's order (ws: cvck_ws_bytes of workspace).
 struct CkCounts {

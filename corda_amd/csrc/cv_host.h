@@ -347,6 +347,7 @@ inline const OptDesc kOpt[CV_OPT_COUNT] = {
     {1, 1, 16},                         // CV_OPT_MID_PIECES
     {2, 2, 4},                          // CV_OPT_PIPE_SLOTS
     {2, 0, 2},                          // CV_OPT_TXS_MERKLE_STREAM
+    {0, 0, 2},                          // CV_OPT_FUSED_KEYED (auto lost to the parent in the measurement of DESIGN.md §5.14)
 };
 
 // A snapshot of a context's options, taken once per call.
@@ -355,7 +356,7 @@ struct Opts {
     size_t pipe_min, pipe_first, pipe_chunk, async_chunk, small_direct_min, shard_min, spread_min, merkle_chunk;
     size_t prep_overlap_min;
     size_t pipe_split, mid_pieces, pipe_slots;
-    int txs_merkle_stream;
+    int txs_merkle_stream, fused_keyed;
     int threads, small_zc, auto_keyed, timeline, pipe_overlap_first;
 };
 
@@ -481,6 +482,7 @@ struct cv_ctx {
         o.mid_pieces = (size_t)opt[CV_OPT_MID_PIECES].load();
         o.pipe_slots = (size_t)opt[CV_OPT_PIPE_SLOTS].load();
         o.txs_merkle_stream = (int)opt[CV_OPT_TXS_MERKLE_STREAM].load();
+        o.fused_keyed = (int)opt[CV_OPT_FUSED_KEYED].load();
         return o;
     }
 };
@@ -533,6 +535,14 @@ int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, 
 hipError_t verify_device_locked(cv_ctx *ctx, Device &d, size_t n, const uint8_t *pk, const uint8_t *sig,
                                 const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint64_t *bitmap,
                                 uint8_t *status, hipStream_t s);
+// cv_api.cpp: the keyed verify of n signatures on stream s of device d — the body of cv_ed25519_verify_device_keyed,
+// for it and for the fused batch calls: the nkeys distinct keys resolved against d's key pool from their host copy
+// hkeys (pool_begin, key_resolve, the slot_of_key upload), cvk_verify_keyed over the device pointers, pool_end.  The
+// caller holds d.mu (cv_resolve_batch through dispatch_one; cv_notarise_batch takes it under its set's mutex).
+// phase_ms as cv_ed25519_verify_device_keyed's; an error leaves nothing queued on s.
+int verify_keyed_locked(cv_ctx *ctx, Device &d, size_t n, size_t nkeys, const uint8_t *hkeys, const uint8_t *d_keys,
+                        const uint32_t *d_key_index, const uint8_t *sig, const uint8_t *arena, const uint64_t *off,
+                        const uint32_t *len, uint64_t *bitmap, uint8_t *status, hipStream_t s, float *phase_ms);
 
 inline Device *find_dev(cv_ctx *ctx, int device) {
     for (auto &d : ctx->devs)

@@ -12,6 +12,7 @@
 //   cv_k_notary.hip the notary's fused commit step (cv_notary.h): gate, state-key gather, finalise + list, scatter
 //   cv_k_tearoff.hip the tear-off verifier and the oracle's signing step (cv_tearoff.h): check bytes, gate, compaction
 //   cv_k_resolve.hip the graph steps of cv_resolve_batch (cv_resolve.h): join-table insert, probe, gate
+//   cv_k_dedupe.hip  the device key dedupe (cv_keydedupe.h): insert, mark, count, scan, emit
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,6 +25,7 @@
 #include "cv_notary.h"
 #include "cv_tearoff.h"
 #include "cv_resolve.h"
+#include "cv_keydedupe.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -200,6 +202,12 @@ __global__ void cv_tearoff_compact_kernel(CvTearoff T, uint32_t *count);
 __global__ void cv_resolve_insert_kernel(CvResolve R);
 __global__ void cv_resolve_probe_kernel(CvResolve R);
 __global__ void cv_resolve_gate_kernel(CvResolve R);
+// the device key dedupe (cv_k_dedupe.hip, cv_keydedupe.h)
+__global__ void cv_dedupe_insert_kernel(CvDedupe D);
+__global__ void cv_dedupe_mark_kernel(CvDedupe D);
+__global__ void cv_dedupe_emit_kernel(CvDedupe D);
+__global__ void cv_dedupe_count_kernel(uint32_t m, const uint32_t *arr, uint32_t *sums);
+__global__ void cv_dedupe_scan_kernel(uint32_t m, uint32_t *arr, const uint32_t *base, uint32_t *total);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

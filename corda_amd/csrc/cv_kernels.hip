@@ -480,6 +480,34 @@ hipError_t cvk_resolve_gate(const CvResolve *R, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ---- the device key dedupe (cv_keydedupe.h).  sums: the levels' block sums (cvd_layout).  The table and stat, which
+// lies behind it, are cleared by one memset; then insert, mark, the compaction of the flags — per level whose entries
+// pass one block a count, the next level, and a scan from the scanned sums; the last level one block — and emit.
+static void dedupe_scan(uint32_t m, uint32_t *arr, uint32_t *const *sums, uint32_t *total, hipStream_t stream) {
+    const dim3 block(CV_BLOCK);
+    if (m <= CVD_SPAN) {
+        hipLaunchKernelGGL(cv_dedupe_scan_kernel, dim3(1), block, 0, stream, m, arr, (const uint32_t *)nullptr, total);
+        return;
+    }
+    const uint32_t nb = (uint32_t)(((uint64_t)m + CVD_SPAN - 1) / CVD_SPAN);
+    hipLaunchKernelGGL(cv_dedupe_count_kernel, dim3(nb), block, 0, stream, m, arr, sums[0]);
+    dedupe_scan(nb, sums[0], sums + 1, total, stream);
+    hipLaunchKernelGGL(cv_dedupe_scan_kernel, dim3(nb), block, 0, stream, m, arr, (const uint32_t *)sums[0],
+                       (uint32_t *)nullptr);
+}
+
+hipError_t cvk_dedupe(const CvDedupe *D, uint32_t *const *sums, hipStream_t stream) {
+    if (!D || D->n == 0 || !sums) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(D->tab, 0xff, 4 * (D->mask + 1) + 4 * CVD_STAT_WORDS, stream);
+    if (e != hipSuccess) return e;
+    const dim3 grid = uniq_grid(D->n), block(CV_BLOCK);
+    hipLaunchKernelGGL(cv_dedupe_insert_kernel, grid, block, 0, stream, *D);
+    hipLaunchKernelGGL(cv_dedupe_mark_kernel, grid, block, 0, stream, *D);
+    dedupe_scan(D->n, D->number, sums, D->stat + CVD_STAT_TOTAL, stream);
+    hipLaunchKernelGGL(cv_dedupe_emit_kernel, grid, block, 0, stream, *D);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

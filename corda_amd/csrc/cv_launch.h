@@ -7,6 +7,7 @@
 #include "cv_ck.h"
 #include "cv_notary.h"
 #include "cv_tearoff.h"
+#include "cv_keydedupe.h"
 #include "cv_resolve.h"
 #include "cv_uniq.h"
 
@@ -125,6 +126,11 @@ hipError_t cvk_tearoff_compact(const CvTearoff *T, uint32_t *count, hipStream_t 
 // missing-signers stages -> outcome, first_bad, bad_input and the counters.  Counts are at most 2^30.
 hipError_t cvk_resolve_join(const CvResolve *R, hipStream_t stream);
 hipError_t cvk_resolve_gate(const CvResolve *R, hipStream_t stream);
+// The device key dedupe (cv_keydedupe.h; kernels in cv_k_dedupe.hip), every step enqueued on `stream`, nothing
+// synchronised: D->pk[n][32] -> D->keys (the distinct keys, first-seen order; rows from the count on are not written),
+// D->key_index[n], *D->nkeys (CVD_NONE after a probe error).  D->stat lies directly behind D->tab (cvd_layout) and
+// sums[CVD_LEVELS] are the levels' block sums; the workspace needs no preparation.  1 <= n <= 0xfffffffe.
+hipError_t cvk_dedupe(const CvDedupe *D, uint32_t *const *sums, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

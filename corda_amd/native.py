@@ -72,6 +72,7 @@ EXPORTED = (
     "cv_uniq_set_max_rounds", "cv_uniq_stats",
     "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
     "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch", "cv_resolve_batch",
+    "cv_ed25519_dedupe_keys_device", "cv_ed25519_dedupe_keys_workspace",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -80,7 +81,7 @@ OPTIONS = {"tri_max": 1, "quad_max": 2, "drain_split": 3, "drain_split_pct": 4, 
            "auto_keyed": 12, "shard_min": 13, "spread_min": 14, "merkle_chunk": 15,
            "prep_overlap_min": 16, "timeline": 17, "pipe_split": 18,
            "pipe_overlap_first": 19, "mid_pieces": 20,
-           "pipe_slots": 21, "txs_merkle_stream": 22}
+           "pipe_slots": 21, "txs_merkle_stream": 22, "fused_keyed": 23}
 STATS = {"pipe": (0, ("plan_s", "pack_s", "wait_s", "enqueue_s", "sync_s", "calls", "subchunks", "direct_subchunks")),
          "small": (1, ("setup_s", "pack_s", "launch_s", "sync_s", "assemble_s", "calls")),
          "route": (2, ("calls", "routed_whole", "split_calls", "shards", "keyed_shards", "keyed_subchunks",
@@ -243,6 +244,11 @@ def load():
         lib.cv_ed25519_verify_device_keyed.argtypes = [_vp, ctypes.c_int, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
                                                        _vp, _vp, _vp, ctypes.POINTER(ctypes.c_float)]
         lib.cv_ed25519_verify_device_keyed.restype = ctypes.c_int
+        if hasattr(lib, "cv_ed25519_dedupe_keys_device"):      # CV_LIB_PATH may name an older build (A/B tooling)
+            lib.cv_ed25519_dedupe_keys_device.argtypes = [_vp, ctypes.c_int, _sz] + [_vp] * 6
+            lib.cv_ed25519_dedupe_keys_device.restype = ctypes.c_int
+            lib.cv_ed25519_dedupe_keys_workspace.argtypes = [_sz]
+            lib.cv_ed25519_dedupe_keys_workspace.restype = ctypes.c_uint64
         lib.cv_calibrate.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         lib.cv_calibrate.restype = ctypes.c_int
         lib.cv_calibrate_cycles.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -633,6 +639,10 @@ class Engine:
         _check(self._lib.cv_get_option(self._h, OPTIONS[name], ctypes.byref(v)), f"cv_get_option({name})")
         return v.value
 
+    def has_option(self, name: str) -> bool:
+        """Whether the loaded library knows the option (CV_LIB_PATH may name an older build)."""
+        return self._lib.cv_get_option(self._h, OPTIONS[name], ctypes.byref(ctypes.c_int64())) == CV_OK
+
     def stats(self, kind: str, reset: bool = False) -> dict:
         which, names = STATS[kind]
         out = (ctypes.c_double * len(names))()
@@ -926,6 +936,15 @@ class Engine:
                "cv_ed25519_verify_device_keyed")
         return tuple(ms) if timed else None
 
+    def dedupe_keys_device(self, device: int, n: int, d_pk: int, d_keys: int, d_key_index: int, d_nkeys: int,
+                           d_workspace: int, stream: int = 0):
+        """The distinct keys of d_pk[n][32] on the device: d_keys (n * 32 bytes, the first nkeys rows written, first-seen
+        order), d_key_index (n uint32), d_nkeys (one uint32); d_workspace of dedupe_keys_workspace(n) bytes.  Enqueues
+        and returns; what verify_device_keyed takes."""
+        _check(self._lib.cv_ed25519_dedupe_keys_device(self._h, device, n, d_pk or None, d_keys or None,
+                                                       d_key_index or None, d_nkeys or None, d_workspace or None,
+                                                       stream or None), "cv_ed25519_dedupe_keys_device")
+
     def sign_device(self, device: int, n: int, d_seed: int, d_arena: int, d_off: int, d_len: int, d_pk: int,
                     d_sig: int, stream: int = 0):
         _check(self._lib.cv_ed25519_sign_device(self._h, device, n, d_seed, d_arena, d_off, d_len, d_pk, d_sig,
@@ -1139,6 +1158,11 @@ def dedupe_keys(pk: np.ndarray):
     if rc < 0:
         raise CvError(rc, "cv_diag_dedupe_keys")
     return (idx, int(nk.value)) if rc == 1 else None
+
+
+def dedupe_keys_workspace(n: int) -> int:
+    """Bytes of device workspace Engine.dedupe_keys_device needs for n keys (host only)."""
+    return int(load().cv_ed25519_dedupe_keys_workspace(n))
 
 
 def tx_verdicts(bitmap: np.ndarray, tx_sig_begin) -> np.ndarray:

@@ -786,6 +786,19 @@ int cv_ed25519_verify_device_keyed(cv_ctx *ctx, int device, size_t n, size_t nke
                                    const void *d_key_index, const void *d_sig, const void *d_arena, const void *d_off,
                                    const void *d_len, void *d_bitmap, void *d_status, void *stream, float *phase_ms);
 
+/* The distinct keys of d_pk[n][32], found on the device: d_keys[nkeys][32] in first-seen order — the
+ * numbering of cv_diag_dedupe_keys — d_key_index[n] (uint32) and *d_nkeys (one uint32), what
+ * cv_ed25519_verify_device_keyed takes for a batch whose keys are already resident.  Two keys are equal iff their 32
+ * bytes are; nothing is decoded.  The result depends on the input bytes alone.  d_keys holds n * 32 bytes (rows from
+ * nkeys on are not written), d_key_index n * 4, d_workspace cv_ed25519_dedupe_keys_workspace(n) bytes (overwritten;
+ * nothing is expected in it); d_nkeys is 4-byte aligned, the others as under the alignment rules above.  Enqueues on
+ * `stream` and returns without synchronising; n == 0 enqueues nothing; n > 0xfffffffe: CV_E_TOO_LARGE.  A probe of
+ * the call's hash table that found no slot — the table's size rules it out — leaves *d_nkeys = 0xffffffff.
+ * cv_ed25519_dedupe_keys_workspace runs on the host and needs no device (0 for n > 0xfffffffe). */
+int cv_ed25519_dedupe_keys_device(cv_ctx *ctx, int device, size_t n, const void *d_pk, void *d_keys, void *d_key_index,
+                                  void *d_nkeys, void *d_workspace, void *stream);
+uint64_t cv_ed25519_dedupe_keys_workspace(size_t n);
+
 int cv_ed25519_sign_device(cv_ctx *ctx, int device, size_t n, const void *d_seed, const void *d_arena,
                            const void *d_off, const void *d_len, void *d_pk, void *d_sig, void *stream);
 
@@ -871,7 +884,13 @@ int cv_calibrate_cycles(cv_ctx *ctx, int device, double *out);
 #define CV_OPT_TXS_MERKLE_STREAM 22 /* cv_verify_transactions: the stream its Merkle groups run on — 0 the compute streams
                                        beside the signature groups, 1 the copy stream behind their leaves, 2 a stream
                                        of their own (default) */
-#define CV_OPT_COUNT 23
+#define CV_OPT_FUSED_KEYED 23       /* cv_notarise_batch (validating) and cv_resolve_batch: the keyed verify path over the
+                                       keys the device dedupe finds — 0 never, 1 auto (more than CV_OPT_TRI_MAX signatures,
+                                       at least eight per distinct key, no more distinct keys than the key pool's
+                                       capacity), 2 whenever the distinct keys fit the pool's capacity.  Every output is
+                                       the same under all three.  Default 0: auto cost a resolve chain more than its keyed
+                                       verify saved */
+#define CV_OPT_COUNT 24
 int cv_set_option(cv_ctx *ctx, int option, int64_t value);
 int cv_get_option(cv_ctx *ctx, int option, int64_t *value);
 

@@ -15,7 +15,13 @@ outputs allocated by the binding inside the timed span for both.  A's C calls ar
 Reports p50 and p99 and the verify-only p50 (cv_ed25519_verify_batch over the same signatures) for scale.
 Writes one JSON record (default profiles/notary_fused.json).  Needs a GPU: no fallback.
 
-    python tools/notary_fused_bench.py [--reps 200] [--out profiles/notary_fused.json]
+--key-pool K signs every record with one of K keys instead of a key of its own (the corpus's rejected records keep
+theirs), the shape the keyed verify route is for; --fused-keyed {0,1,2} sets CV_OPT_FUSED_KEYED for the run (0 on a
+library from before the option — CV_LIB_PATH — changes nothing: that library has only the unkeyed route).  With either
+argument the record names both and every timing also carries its quartiles; without them the shape
+and the record are as before.
+
+    python tools/notary_fused_bench.py [--reps 200] [--out profiles/notary_fused.json] [--key-pool K] [--fused-keyed M]
 """
 import argparse
 import hashlib
@@ -37,11 +43,19 @@ K = 25
 NO_SIG = native.NS_NO_SIG
 
 
-def make(engine, ntx, seed, adversarial):
+QUARTILES = False                   # --key-pool / --fused-keyed: pct() adds p25 and p75
+
+
+def make(engine, ntx, seed, adversarial, key_pool=0):
     tb = workload.make_tx_batch(engine, 0, ntx, signers=SIGNERS, seed=seed)
     h = lambda t, dt: t.cpu().numpy().astype(dt)
     n = ntx * SIGNERS
     pk, sig = h(tb.sigs.pk, np.uint8), h(tb.sigs.sig, np.uint8)
+    if key_pool:                    # the same pool for every batch of the run, so its keys stay resident
+        pool = np.random.default_rng(key_pool).integers(0, 256, (key_pool, 32), dtype=np.uint8)
+        who = np.random.default_rng(seed).integers(0, key_pool, n)
+        pk, sig = engine.sign_batch(pool[who], h(tb.ids, np.uint8).reshape(-1), (np.arange(n, dtype=np.uint64) // SIGNERS) * 32,
+                                    np.full(n, 32, np.uint32))
     apk, asig, _ = adversarial
     for j, i in enumerate(range(seed % 16, n, 16)):
         pk[i], sig[i] = apk[j % len(apk)], asig[j % len(apk)]
@@ -107,13 +121,16 @@ def run_b(engine, uniq, signer, b):
 
 def pct(xs):
     xs = np.sort(np.array(xs)) * 1e3
-    return {"p50_ms": float(np.percentile(xs, 50)), "p99_ms": float(np.percentile(xs, 99)), "min_ms": float(xs[0]),
-            "reps": int(xs.size)}
+    r = {"p50_ms": float(np.percentile(xs, 50)), "p99_ms": float(np.percentile(xs, 99)), "min_ms": float(xs[0]),
+         "reps": int(xs.size)}
+    if QUARTILES:
+        r.update(p25_ms=float(np.percentile(xs, 25)), p75_ms=float(np.percentile(xs, 75)))
+    return r
 
 
-def one_size(engine, signer, nsig, reps, adversarial):
+def one_size(engine, signer, nsig, reps, adversarial, key_pool=0):
     ntx = nsig // SIGNERS
-    batches = [make(engine, ntx, 1000 * nsig + j, adversarial) for j in range(K + 1)]
+    batches = [make(engine, ntx, 1000 * nsig + j, adversarial, key_pool) for j in range(K + 1)]
     ta, tb, tac, tv, sets = [], [], [], [], []
     accepted = None
     for rep in range(reps):
@@ -153,7 +170,11 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--sizes", type=int, nargs="*", default=list(SIZES))
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "notary_fused.json"))
+    ap.add_argument("--key-pool", type=int, default=None, help="signers drawn from this many keys")
+    ap.add_argument("--fused-keyed", type=int, choices=(0, 1, 2), default=None, help="CV_OPT_FUSED_KEYED for the run")
     a = ap.parse_args()
+    global QUARTILES
+    QUARTILES = a.key_pool is not None or a.fused_keyed is not None
     if a.reps < 200:
         raise SystemExit("at least 200 repetitions")
     if not torch.cuda.is_available():
@@ -165,9 +186,15 @@ def main():
            "timer": "perf_counter around the synchronous calls through the ctypes binding, host buffers (pageable); A and B "
                     "interleaved per repetition on the same batch, the order alternating",
            "sizes": []}
+    if QUARTILES:
+        has = "fused_keyed" in native.OPTIONS and engine.has_option("fused_keyed")
+        if a.fused_keyed is not None and (has or a.fused_keyed != 0):
+            engine.set_option("fused_keyed", a.fused_keyed)
+        rec.update(key_pool=a.key_pool or 0, fused_keyed=engine.get_option("fused_keyed") if has else 0,
+                   library_has_fused_keyed=has, library=native.LIB_PATH)
     ok = True
     for n in a.sizes:
-        r = one_size(engine, signer, n, a.reps, adversarial)
+        r = one_size(engine, signer, n, a.reps, adversarial, a.key_pool or 0)
         rec["sizes"].append(r)
         ok &= r["b_fused"]["p50_ms"] <= r["a_five_calls"]["p50_ms"]
         print(f"sigs={n:6d}  A five calls p50 {r['a_five_calls']['p50_ms']:.3f} p99 {r['a_five_calls']['p99_ms']:.3f} ms "

@@ -18,7 +18,12 @@ stages of one further, untimed call (CV_OPT_TIMELINE, cv_diag_stats CV_STATS_RES
 Acceptance at 5,000 transactions: p50(a) <= 1.10 x p50(b).  Writes one JSON record (default
 profiles/resolve_fused.json).  Needs a GPU: no fallback.
 
-    python tools/resolve_fused_bench.py [--reps 200] [--out profiles/resolve_fused.json]
+--key-pool K draws each transaction's two signers from K keys instead of the chain's two parties; --fused-keyed {0,1,2}
+sets CV_OPT_FUSED_KEYED for the run (0 on a library from before the option — CV_LIB_PATH — changes nothing: that
+library has only the unkeyed route).  With either argument the record names both and every timing also carries its
+quartiles; without them the shape and the record are as before.
+
+    python tools/resolve_fused_bench.py [--reps 200] [--out profiles/resolve_fused.json] [--key-pool K] [--fused-keyed M]
 """
 import argparse
 import hashlib
@@ -39,6 +44,7 @@ from corda_amd.transactions import SecureHash, SignedTransaction, WireTransactio
 SIZES = (256, 5000, 65536)
 ACCEPT_AT, ACCEPT = 5000, 1.10
 LEAVES, SIGNERS = 6, 2
+QUARTILES = False                   # --key-pool / --fused-keyed: pct() adds p25 and p75
 
 
 def host_id(leaves) -> bytes:
@@ -55,18 +61,32 @@ def make_chain(keys, ntx, seed):
     """-> the downloads, the newest first.  Built oldest first: an input names its predecessor's id."""
     rng = np.random.default_rng(seed)
     prev = SecureHash(hashlib.sha256(b"genesis %d" % seed).digest())
-    must = [k.public.composite for k in keys]
+    # two parties: both sign everything; a pool: transaction t is signed by keys 2t and 2t + 1 of it, in turn
+    pair = lambda t: keys if len(keys) == SIGNERS else [keys[(SIGNERS * t + j) % len(keys)] for j in range(SIGNERS)]
     wtxs = []
     for t in range(ntx):
+        must = [k.public.composite for k in pair(t)]
         blob = lambda tag: bytes(rng.integers(0, 256, int(rng.integers(40, 200)), dtype=np.uint8)) + tag
         w = WireTransaction(inputs=[resolve.StateRef(prev, 0).blob], outputs=[blob(b"o0"), blob(b"o1")],
                             commands=[blob(b"c0"), blob(b"c1"), blob(b"c2")], must_sign=must)
         w._id = prev = SecureHash(host_id(w.leaves))
         wtxs.append(w)
-    sigs = [k.sign_many([w._id.bytes for w in wtxs]) for k in keys]
+    if len(keys) == SIGNERS:
+        sigs = [k.sign_many([w._id.bytes for w in wtxs]) for k in keys]
+        of = lambda t: [s[t] for s in sigs]
+    else:                                                          # each key signs the transactions it is a party to
+        by_tx = [[None] * SIGNERS for _ in range(ntx)]
+        work = [[] for _ in keys]
+        for t in range(ntx):
+            for j in range(SIGNERS):
+                work[(SIGNERS * t + j) % len(keys)].append((t, j))
+        for k, mine in zip(keys, work):
+            for (t, j), s in zip(mine, k.sign_many([wtxs[t]._id.bytes for t, _ in mine]) if mine else []):
+                by_tx[t][j] = s
+        of = lambda t: list(by_tx[t])
     stxs = []
     for t, w in enumerate(wtxs):
-        mine = [s[t] for s in sigs]
+        mine = of(t)
         if t % 16 == seed % 16:
             bad = bytearray(mine[0].bits)
             bad[40] ^= 1
@@ -87,8 +107,11 @@ def run_b(engine, args):
 
 def pct(xs):
     xs = np.sort(np.array(xs)) * 1e3
-    return {"p50_ms": float(np.percentile(xs, 50)), "p99_ms": float(np.percentile(xs, 99)), "min_ms": float(xs[0]),
-            "reps": int(xs.size)}
+    r = {"p50_ms": float(np.percentile(xs, 50)), "p99_ms": float(np.percentile(xs, 99)), "min_ms": float(xs[0]),
+         "reps": int(xs.size)}
+    if QUARTILES:
+        r.update(p25_ms=float(np.percentile(xs, 25)), p75_ms=float(np.percentile(xs, 75)))
+    return r
 
 
 def one_size(engine, keys, ntx, reps):
@@ -143,16 +166,28 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--sizes", type=int, nargs="*", default=list(SIZES))
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "resolve_fused.json"))
+    ap.add_argument("--key-pool", type=int, default=None, help="signers drawn from this many keys (at least 2)")
+    ap.add_argument("--fused-keyed", type=int, choices=(0, 1, 2), default=None, help="CV_OPT_FUSED_KEYED for the run")
     a = ap.parse_args()
+    global QUARTILES
+    QUARTILES = a.key_pool is not None or a.fused_keyed is not None
+    if a.key_pool is not None and a.key_pool < SIGNERS:
+        raise SystemExit("--key-pool: at least 2 keys")
     if not torch.cuda.is_available():
         raise SystemExit("resolve_fused_bench needs a GPU")
     engine = native.Engine(1)
-    keys = [KeyPair(hashlib.sha256(b"resolve bench key %d" % k).digest(), engine) for k in range(SIGNERS)]
+    keys = [KeyPair(hashlib.sha256(b"resolve bench key %d" % k).digest(), engine) for k in range(a.key_pool or SIGNERS)]
     rec = {"tool": "tools/resolve_fused_bench.py", "device": torch.cuda.get_device_name(0), "reps": a.reps,
            "timer": "perf_counter around the synchronous calls through the ctypes binding, host buffers (pageable); the "
                     "variants interleaved per repetition on the same batch, the order rotating; stages: HIP events around "
                     "the stages of one untimed call",
            "sizes": []}
+    if QUARTILES:
+        has = "fused_keyed" in native.OPTIONS and engine.has_option("fused_keyed")
+        if a.fused_keyed is not None and (has or a.fused_keyed != 0):
+            engine.set_option("fused_keyed", a.fused_keyed)
+        rec.update(key_pool=a.key_pool or SIGNERS, fused_keyed=engine.get_option("fused_keyed") if has else 0,
+                   library_has_fused_keyed=has, library=native.LIB_PATH)
     ok = None
     for n in a.sizes:
         r = one_size(engine, keys, n, a.reps)
