@@ -9,6 +9,8 @@ extern "C" {
 
 // ---------------------------------------------------------------- uniqueness set (the notary's commit step)
 
+#define CV_UNIQ_SNAP_BLOCK 256u   // slots per block of the snapshot's kernels (cv_k_uniq.hip: CV_BLOCK)
+
 static size_t uniq_slots(size_t capacity) {
     size_t s = 16;
     while (s < 2 * capacity) s <<= 1;
@@ -73,6 +75,7 @@ uint32_t uniq_bmask(size_t nstates) {
 // and the tail looks for itself), report + insert.  Shared by cv_uniq_commit_batch and cv_notarise_batch.
 int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, uint64_t *rounds_out) {
     hipStream_t s = u->stream;
+    u->touch();                                                  // a commit may insert: passes of a snapshot end here
     CV_TRY(cvk_uniq_front(&u->T, &B, cur, s));
     uint64_t rounds = 0;
     bool undecided = true;
@@ -103,6 +106,7 @@ int cv_uniq_open(cv_ctx *ctx, int device, size_t capacity_states, cv_uniq **out)
     u->capacity = std::max<size_t>(capacity_states, 1);
     std::random_device rd;
     const uint64_t seed = key_seed(0) ^ (((uint64_t)rd() << 32) | rd());
+    u->epoch = (((uint64_t)rd() << 32) | rd()) | 1;              // a cursor of another set does not continue on this one
     int rc = hip_rc(hipSetDevice(u->ordinal));
     if (rc == CV_OK) rc = hip_rc(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
     if (rc == CV_OK) rc = hip_rc(hipHostMalloc(reinterpret_cast<void **>(&u->hstat), 4 * CVU_D_WORDS, hipHostMallocDefault));
@@ -158,6 +162,7 @@ int cv_uniq_reserve(cv_uniq *u, size_t capacity_states) {
     u->tab = base;
     u->T = to;
     u->capacity = capacity_states;
+    u->touch();                                                  // the slots moved
     return CV_OK;
 }
 
@@ -283,16 +288,10 @@ int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key, uint8_t *foun
     return rc;
 }
 
-int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *consumed_id,
-                 const uint32_t *consumed_index, const uint32_t *consumed_caller) {
-    if (n == 0) return CV_OK;
-    if (n > 0xfffffffeull) return CV_E_TOO_LARGE;
-    if (!state_key || !consumed_id || !consumed_index || !consumed_caller) return CV_E_ARGS;
-    if (n > kUniqMaxStates) return CV_E_TOO_LARGE;
-    if (!u) return CV_E_ARGS;
-    std::lock_guard<std::mutex> g(u->mu);
-    if (u->resident + n > u->capacity) return CV_E_OOM;
-    CV_TRY(hipSetDevice(u->ordinal));
+// n rows into table T of the set's device (the set's own, or a fresh one beside it) on the set's stream: the check
+// first (a key repeated in the call, or resident in T: CV_E_ARGS, T unchanged), then the inserts.  Synchronises.
+static int uniq_load_into(cv_uniq *u, const CvUniqTable &T, size_t n, const uint8_t *state_key, const uint8_t *consumed_id,
+                          const uint32_t *consumed_index, const uint32_t *consumed_caller) {
     const size_t bs = (size_t)uniq_bmask(n) + 1;
     Layout lay;
     const size_t o_key = lay.take(32 * n), o_id = lay.take(32 * n), o_ix = lay.take(4 * n), o_cal = lay.take(4 * n);
@@ -318,8 +317,8 @@ int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *
     B.rep = at<uint32_t>(base, o_rep);
     B.res = at<uint32_t>(base, o_res);
     B.dstat = u->dstat.as<uint32_t>();
-    // the check first (a key repeated in the call, or resident): the set changes only after it passed
-    CV_TRY(cvk_uniq_load(&u->T, &B, 0, s));
+    // the check first (a key repeated in the call, or resident): the table changes only after it passed
+    CV_TRY(cvk_uniq_load(&T, &B, 0, s));
     rc = uniq_stat_read(u);
     if (rc != CV_OK) return rc;
     if (u->hstat[CVU_D_ERROR]) {
@@ -330,11 +329,134 @@ int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *
         drain.armed = false;
         return CV_E_ARGS;
     }
-    CV_TRY(cvk_uniq_load(&u->T, &B, 1, s));
+    CV_TRY(cvk_uniq_load(&T, &B, 1, s));
     rc = uniq_stat_end(u);
     drain.armed = false;
+    return rc;
+}
+
+int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *consumed_id,
+                 const uint32_t *consumed_index, const uint32_t *consumed_caller) {
+    if (n == 0) return CV_OK;
+    if (n > 0xfffffffeull) return CV_E_TOO_LARGE;
+    if (!state_key || !consumed_id || !consumed_index || !consumed_caller) return CV_E_ARGS;
+    if (n > kUniqMaxStates) return CV_E_TOO_LARGE;
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    if (u->resident + n > u->capacity) return CV_E_OOM;
+    CV_TRY(hipSetDevice(u->ordinal));
+    u->touch();
+    const int rc = uniq_load_into(u, u->T, n, state_key, consumed_id, consumed_index, consumed_caller);
     if (rc == CV_OK) u->resident += n;
     return rc;
+}
+
+// The slot window of one snapshot call: what the load factor of 1/2 makes room for max_entries records, and no less
+// than 65,536 slots, so a pass with a small buffer costs about resident / max_entries calls.
+static uint64_t snap_window(uint64_t max_entries) { return std::max<uint64_t>(2 * max_entries, 65536); }
+
+int cv_uniq_snapshot(cv_uniq *u, uint64_t cursor[2], size_t max_entries, uint8_t *state_key, uint8_t *consumed_id,
+                     uint32_t *consumed_index, uint32_t *consumed_caller, size_t *n) {
+    if (max_entries == 0 || !cursor || !n || !state_key || !consumed_id || !consumed_index || !consumed_caller)
+        return CV_E_ARGS;
+    if (max_entries > kUniqMaxStates) return CV_E_TOO_LARGE;
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    if (cursor[0] == UINT64_MAX) {                               // a finished pass: nothing more
+        *n = 0;
+        return CV_OK;
+    }
+    const uint64_t slots = (uint64_t)u->T.mask + 1;
+    if (cursor[0] == 0 ? cursor[1] != 0 : (cursor[1] != u->epoch || cursor[0] >= slots)) return CV_E_ARGS;
+    CV_TRY(hipSetDevice(u->ordinal));
+    const uint64_t b = cursor[0], e = std::min(slots, b + snap_window(max_entries));
+    const size_t m = (size_t)std::min<uint64_t>(max_entries, e - b);   // a window holds no more records than slots
+    // records | result words | the levels of block totals
+    Layout lay;
+    const size_t o_key = lay.take(32 * m), o_id = lay.take(32 * m), o_ix = lay.take(4 * m), o_cal = lay.take(4 * m);
+    const size_t o_out = lay.take(4 * CVU_SNAP_WORDS);
+    size_t o_sum[CVD_LEVELS];
+    uint64_t w = (e - b + CV_UNIQ_SNAP_BLOCK - 1) / CV_UNIQ_SNAP_BLOCK;
+    for (int k = 0; k < CVD_LEVELS; k++) {
+        o_sum[k] = lay.take(4 * (size_t)w);
+        w = cvd_blocks(w);
+    }
+    CV_TRY(u->ws.ensure(lay.top + 16));
+    uint8_t *base = u->ws.as<uint8_t>();
+    hipStream_t s = u->stream;
+    auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
+    CvUniqSnap S{};
+    S.slot_begin = (uint32_t)b;
+    S.slot_end = (uint32_t)e;
+    S.max_entries = (uint32_t)max_entries;
+    S.key = at<uint32_t>(base, o_key);
+    S.id = at<uint32_t>(base, o_id);
+    S.index = at<uint32_t>(base, o_ix);
+    S.caller = at<uint32_t>(base, o_cal);
+    S.out = at<uint32_t>(base, o_out);
+    uint32_t *sums[CVD_LEVELS];
+    for (int k = 0; k < CVD_LEVELS; k++) sums[k] = at<uint32_t>(base, o_sum[k]);
+    CV_TRY(cvk_uniq_snapshot(&u->T, &S, sums, s));
+    // the two words first: only the records they count are copied, straight into the caller's arrays
+    CV_TRY(hipMemcpyAsync(u->hstat, S.out, 4 * CVU_SNAP_WORDS, hipMemcpyDeviceToHost, s));
+    CV_TRY(hipStreamSynchronize(s));
+    const size_t cnt = u->hstat[CVU_SNAP_COUNT];
+    const uint64_t next = u->hstat[CVU_SNAP_NEXT];
+    if (cnt > m || next <= b || next > e) return CV_E_HIP;
+    if (cnt) {
+        CV_TRY(hipMemcpyAsync(state_key, base + o_key, 32 * cnt, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipMemcpyAsync(consumed_id, base + o_id, 32 * cnt, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipMemcpyAsync(consumed_index, base + o_ix, 4 * cnt, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipMemcpyAsync(consumed_caller, base + o_cal, 4 * cnt, hipMemcpyDeviceToHost, s));
+        CV_TRY(hipStreamSynchronize(s));
+    }
+    drain.armed = false;
+    *n = cnt;
+    cursor[0] = next == slots ? UINT64_MAX : next;
+    cursor[1] = u->epoch;
+    return CV_OK;
+}
+
+int cv_uniq_clear(cv_uniq *u) {
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    CV_TRY(hipSetDevice(u->ordinal));
+    u->touch();
+    CV_TRY(hipMemsetAsync(u->T.occ, 0, 4 * ((size_t)u->T.mask + 1), u->stream));
+    CV_TRY(hipStreamSynchronize(u->stream));
+    u->resident = 0;
+    return CV_OK;
+}
+
+int cv_uniq_install(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_t *consumed_id,
+                    const uint32_t *consumed_index, const uint32_t *consumed_caller) {
+    if (n == 0) return cv_uniq_clear(u);
+    if (!state_key || !consumed_id || !consumed_index || !consumed_caller) return CV_E_ARGS;
+    if (n > kUniqMaxStates) return CV_E_TOO_LARGE;
+    if (!u) return CV_E_ARGS;
+    std::lock_guard<std::mutex> g(u->mu);
+    CV_TRY(hipSetDevice(u->ordinal));
+    // a fresh table beside the old one, as cv_uniq_reserve builds it: the old one serves until the new one is whole
+    const size_t capacity = std::max(u->capacity, n);
+    std::random_device rd;
+    const uint64_t seed = key_seed(0) ^ (((uint64_t)rd() << 32) | rd());
+    void *base = nullptr;
+    CvUniqTable to{};
+    int rc = uniq_alloc(capacity, seed, u->stream, &base, &to);
+    if (rc != CV_OK) return rc;
+    rc = uniq_load_into(u, to, n, state_key, consumed_id, consumed_index, consumed_caller);
+    if (rc != CV_OK) {
+        (void)hipStreamSynchronize(u->stream);
+        (void)hipFree(base);                                     // the old table is untouched
+        return rc;
+    }
+    (void)hipFree(u->tab);
+    u->tab = base;
+    u->T = to;
+    u->capacity = capacity;
+    u->resident = n;
+    u->touch();
+    return CV_OK;
 }
 
 }  // extern "C"

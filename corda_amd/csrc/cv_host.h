@@ -512,6 +512,12 @@ struct cv_uniq {
     uint32_t *hstat = nullptr;               // pinned: the device counters read back
     int max_rounds = 8;
     uint64_t last_rounds = 0, last_tail = 0, last_probe = 0, wraps = 0;
+    // advanced by every call that may change the table's contents or layout (commit, load, install, clear, a reserve
+    // that rehashes); a snapshot cursor carries the value of the call that started its pass.  Never 0.
+    uint64_t epoch = 1;
+    void touch() {
+        if (++epoch == 0) epoch = 1;
+    }
     // cv_notarise_batch (cv_api_notary.cpp): its inputs packed in pinned memory for one upload, its device copy of them
     // with the pipeline's workspace and outputs behind, and the pinned block the outputs come back through
     cvh::PinBuf nin, nout;

@@ -1,6 +1,7 @@
 // cv_k_uniq.hip — the notary's uniqueness set (f4 / a11, the commit step): one kernel per step of cv_uniq.h.
 // Shared helpers and every kernel declaration: cv_kcommon.h; launchers: cv_kernels.hip (cvk_uniq_*).
-// No kernel here waits for another lane's store, and every probe loop is bounded by its table's slot count.
+// No kernel here waits for another lane's store, and every probe loop is bounded by its table's slot count.  The
+// snapshot's kernels meet their block at one barrier each, which every lane reaches.
 #include "cv_kcommon.h"
 
 // the sum of v over the wave's lanes, in lane 0 (every lane of the wave calls it)
@@ -84,4 +85,39 @@ __global__ __launch_bounds__(CV_BLOCK) void cv_uniq_lookup_kernel(CvUniqTable T,
 __global__ __launch_bounds__(CV_BLOCK) void cv_uniq_rehash_kernel(CvUniqTable from, CvUniqTable to, uint32_t *dstat) {
     const uint64_t s = (uint64_t)blockIdx.x * CV_BLOCK + threadIdx.x;
     if (s <= from.mask) cvu_rehash(from, to, (uint32_t)s, dstat);
+}
+
+// ---- snapshot (cv_uniq.h): one lane per slot of the window, CV_BLOCK slots a block
+// the lane's flag -> (occupied slots in the lanes of the block before this one, the block's total when `total`)
+static __device__ __forceinline__ uint32_t cvu_block_rank(bool occ, uint32_t *wsum, uint32_t *total) {
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(occ);
+    if (lane == 0) wsum[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < CV_BLOCK / 64; k++) {
+        before += k < wv ? wsum[k] : 0u;
+        all += wsum[k];
+    }
+    if (total) *total = all;
+    return before;
+}
+
+__global__ __launch_bounds__(CV_BLOCK) void cv_uniq_snap_count_kernel(CvUniqTable T, CvUniqSnap S, uint32_t *__restrict__ sums) {
+    __shared__ uint32_t wsum[CV_BLOCK / 64];
+    const uint32_t i = blockIdx.x * CV_BLOCK + threadIdx.x;
+    uint32_t total = 0;
+    (void)cvu_block_rank(cvu_snap_occupied(T, S, i) != 0, wsum, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// base: the scanned block totals.  A wave's occupied lanes hold consecutive ranks, so their records are adjacent.
+__global__ __launch_bounds__(CV_BLOCK) void cv_uniq_snap_emit_kernel(CvUniqTable T, CvUniqSnap S, const uint32_t *__restrict__ base) {
+    __shared__ uint32_t wsum[CV_BLOCK / 64];
+    const uint32_t i = blockIdx.x * CV_BLOCK + threadIdx.x;
+    const bool occ = cvu_snap_occupied(T, S, i) != 0;
+    const uint32_t rank = base[blockIdx.x] + cvu_block_rank(occ, wsum, nullptr);
+    if (occ) cvu_snap_emit(T, S, i, rank);
+    if (i == 0) cvu_snap_close(S);
 }

@@ -7,7 +7,8 @@
 //   cv_k_misc.hip  signing (synthetic inputs), Merkle ids, partial Merkle trees, calibration kernels
 //   cv_k_sign.hip  fixed-key signing (signer key expansion, one signature per lane)
 //   cv_k_pmt.hip   partial Merkle tree build (tear-offs): count, scan, emit
-//   cv_k_uniq.hip  the notary's uniqueness set (cv_uniq.h): group, rounds, tail, report + insert, load, lookup, rehash
+//   cv_k_uniq.hip  the notary's uniqueness set (cv_uniq.h): group, rounds, tail, report + insert, load, lookup, rehash,
+//                  snapshot
 //   cv_k_ck.hip    missing signers (cv_ck.h): one lane per transaction, one wave per large transaction
 //   cv_k_notary.hip the notary's fused commit step (cv_notary.h): gate, state-key gather, finalise + list, scatter
 //   cv_k_tearoff.hip the tear-off verifier and the oracle's signing step (cv_tearoff.h): check bytes, gate, compaction
@@ -186,6 +187,8 @@ __global__ void cv_uniq_load_check_kernel(CvUniqBatch B);
 __global__ void cv_uniq_load_put_kernel(CvUniqTable T, CvUniqBatch B);
 __global__ void cv_uniq_lookup_kernel(CvUniqTable T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id, uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat);
 __global__ void cv_uniq_rehash_kernel(CvUniqTable from, CvUniqTable to, uint32_t *dstat);
+__global__ void cv_uniq_snap_count_kernel(CvUniqTable T, CvUniqSnap S, uint32_t *sums);
+__global__ void cv_uniq_snap_emit_kernel(CvUniqTable T, CvUniqSnap S, const uint32_t *base);
 // missing signers (cv_k_ck.hip, cv_ck.h): the wide kernel's workgroups are one wave
 __global__ void cv_ck_narrow_kernel(CvCk C);
 __global__ void cv_ck_wide_kernel(CvCk C);

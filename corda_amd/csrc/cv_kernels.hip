@@ -508,6 +508,19 @@ hipError_t cvk_dedupe(const CvDedupe *D, uint32_t *const *sums, hipStream_t stre
     return hipGetLastError();
 }
 
+// The snapshot of a window of the uniqueness set (cv_uniq.h): count, the scan of the block totals (the dedupe's, which
+// also writes the window's total) and emit.  sums: CVD_LEVELS arrays, the first of one word per CV_BLOCK slots of the
+// window, each next of one word per CVD_SPAN words of the one before.
+hipError_t cvk_uniq_snapshot(const CvUniqTable *T, const CvUniqSnap *S, uint32_t *const *sums, hipStream_t stream) {
+    if (!T || !S || !sums || S->slot_end <= S->slot_begin || (uint64_t)S->slot_end > (uint64_t)T->mask + 1 || S->max_entries == 0)
+        return hipErrorInvalidValue;
+    const uint32_t nb = (uint32_t)(((uint64_t)(S->slot_end - S->slot_begin) + CV_BLOCK - 1) / CV_BLOCK);
+    hipLaunchKernelGGL(cv_uniq_snap_count_kernel, dim3(nb), dim3(CV_BLOCK), 0, stream, *T, *S, sums[0]);
+    dedupe_scan(nb, sums[0], sums + 1, S->out + CVU_SNAP_TOTAL, stream);
+    hipLaunchKernelGGL(cv_uniq_snap_emit_kernel, dim3(nb), dim3(CV_BLOCK), 0, stream, *T, *S, (const uint32_t *)sums[0]);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

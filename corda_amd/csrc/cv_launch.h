@@ -90,6 +90,7 @@ hipError_t cvk_pmt_build(uint32_t ntx, const CvkPmtBuild *a, hipStream_t stream)
 //   load  : phase 0 clears the batch table, groups the keys and looks them up (dstat[CVU_D_BAD] if one repeats or
 //           is resident); phase 1 inserts them
 //   rehash: one lane per slot of `from` re-inserts into `to` (occ of `to` zero before)
+//   snapshot: count, scan and emit over the window of S; sums: CVD_LEVELS arrays of block totals (cv_kernels.hip)
 hipError_t cvk_uniq_front(const CvUniqTable *T, const CvUniqBatch *B, uint32_t *stat, hipStream_t stream);
 hipError_t cvk_uniq_round(const CvUniqBatch *B, const uint32_t *stat_in, uint32_t *stat_out, uint32_t round,
                           hipStream_t stream);
@@ -98,6 +99,7 @@ hipError_t cvk_uniq_load(const CvUniqTable *T, const CvUniqBatch *B, int phase, 
 hipError_t cvk_uniq_lookup(const CvUniqTable *T, uint32_t n, const uint32_t *key, uint8_t *found, uint32_t *cons_id,
                            uint32_t *cons_index, uint32_t *cons_caller, uint32_t *dstat, hipStream_t stream);
 hipError_t cvk_uniq_rehash(const CvUniqTable *from, const CvUniqTable *to, uint32_t *dstat, hipStream_t stream);
+hipError_t cvk_uniq_snapshot(const CvUniqTable *T, const CvUniqSnap *S, uint32_t *const *sums, hipStream_t stream);
 // Missing signers of a->ntx transactions (cv_ck.h; kernels in cv_k_ck.hip), enqueued on `stream`, nothing synchronised:
 // the list's counter cleared, the narrow kernel, then (unless wide_min is UINT32_MAX) the wide kernel over the list.
 // a->wide_min == 0 takes the default; count, list and flag point into the caller's workspace (cvck_ws_bytes).

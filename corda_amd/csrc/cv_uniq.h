@@ -34,6 +34,17 @@
 // first slot whose atomicCAS(occ, 0, tag) succeeds, without a key compare, and writes key and record with plain
 // stores; the kernel boundary publishes them (no lane of the inserting kernel reads a slot that was empty before it).
 //
+// SNAPSHOT (DistributedImmutableMap.snapshot): an ordered stream compaction of the occupied slots of a window
+// [slot_begin, slot_end) of the resident table, one lane per slot, the table read-only:
+//   count   per block: the occupied slots of its lanes (a ballot and a popcount per wave, the wave totals through LDS)
+//   scan    the block totals -> their exclusive prefix sums and the window's total (the key dedupe's hierarchical scan)
+//   emit    an occupied slot's rank r = block base + the waves before it + the lanes before it, so ranks ascend with
+//           the slot: r < max_entries writes record r (key, id, index, caller: the committed words), r == max_entries
+//           stores its slot as the next cursor; one lane closes: count = min(total, max_entries), and the next cursor
+//           is slot_end when no lane has rank max_entries.  Every output word has exactly one writer.
+// The records are a function of the table and the window alone.  INSTALL builds a fresh table with the load path
+// (cvu_group with stat == null, cvu_load_check, cvu_load_put) and the host swaps the tables; CLEAR zeroes occ.
+//
 // NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE LOOP IS BOUNDED by its table's slot count and
 // sets dstat[CVU_D_ERROR] when it runs out (the host returns CV_E_HIP).
 #pragma once
@@ -67,6 +78,19 @@ struct CvUniqTable {
     uint32_t *occ, *key, *id, *index, *caller;
     uint32_t mask;                // slots - 1
     uint64_t seed;
+};
+
+// words of a snapshot call's device result
+#define CVU_SNAP_NEXT 0           // the slot the next call starts at (slot_end: the window is done)
+#define CVU_SNAP_COUNT 1          // records written: min(total, max_entries)
+#define CVU_SNAP_TOTAL 2          // occupied slots of the window (the scan writes it)
+#define CVU_SNAP_WORDS 4
+
+struct CvUniqSnap {
+    uint32_t slot_begin, slot_end;                // the window, slot_end <= the slot count
+    uint32_t max_entries;                         // at least 1
+    uint32_t *key, *id, *index, *caller;          // min(max_entries, slot_end - slot_begin) records
+    uint32_t *out;                                // CVU_SNAP_WORDS
 };
 
 struct CvUniqBatch {
@@ -339,4 +363,35 @@ CV_HD void cvu_load_check(const CvUniqBatch &B, uint32_t i) {
 }
 CV_HD void cvu_load_put(const CvUniqTable &T, const CvUniqBatch &B, uint32_t i) {
     cvu_insert(T, B.key + 8 * (size_t)i, B.id + 8 * (size_t)i, B.cons_index[i], B.caller[i], B.dstat);
+}
+
+// ---- snapshot: the per-lane pieces of count and emit (the header comment); the scan between them is the caller's
+CV_HD uint32_t cvu_snap_occupied(const CvUniqTable &T, const CvUniqSnap &S, uint32_t i) {
+    return i < S.slot_end - S.slot_begin && T.occ[S.slot_begin + i] != 0;
+}
+// eight words between 16-byte aligned places (a table's arrays and a call's buffers are): two 16-byte moves on the device
+CV_HD void cvu_copy8_aligned(uint32_t *d, const uint32_t *s) {
+#ifdef __HIP_DEVICE_COMPILE__
+    d = static_cast<uint32_t *>(__builtin_assume_aligned(d, 16));
+    s = static_cast<const uint32_t *>(__builtin_assume_aligned(s, 16));
+#endif
+    cvu_copy8(d, s);
+}
+// lane i of the window holds an occupied slot, the rank-th of the window
+CV_HD void cvu_snap_emit(const CvUniqTable &T, const CvUniqSnap &S, uint32_t i, uint32_t rank) {
+    const uint32_t slot = S.slot_begin + i;
+    if (rank < S.max_entries) {
+        cvu_copy8_aligned(S.key + 8 * (size_t)rank, T.key + 8 * (size_t)slot);
+        cvu_copy8_aligned(S.id + 8 * (size_t)rank, T.id + 8 * (size_t)slot);
+        S.index[rank] = T.index[slot];
+        S.caller[rank] = T.caller[slot];
+    } else if (rank == S.max_entries) {
+        S.out[CVU_SNAP_NEXT] = slot;
+    }
+}
+// ONE lane, after the scan wrote the total
+CV_HD void cvu_snap_close(const CvUniqSnap &S) {
+    const uint32_t total = S.out[CVU_SNAP_TOTAL];
+    S.out[CVU_SNAP_COUNT] = total < S.max_entries ? total : S.max_entries;
+    if (total <= S.max_entries) S.out[CVU_SNAP_NEXT] = S.slot_end;
 }

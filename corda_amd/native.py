@@ -69,7 +69,7 @@ EXPORTED = (
     "cv_signer_open", "cv_signer_public_key", "cv_signer_close", "cv_ed25519_sign_keyed",
     "cv_ed25519_sign_keyed_device", "cv_partial_merkle_build_bound", "cv_partial_merkle_build", "cv_filtered_build",
     "cv_uniq_open", "cv_uniq_close", "cv_uniq_reserve", "cv_uniq_commit_batch", "cv_uniq_lookup", "cv_uniq_load",
-    "cv_uniq_set_max_rounds", "cv_uniq_stats",
+    "cv_uniq_set_max_rounds", "cv_uniq_stats", "cv_uniq_snapshot", "cv_uniq_clear", "cv_uniq_install",
     "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
     "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch", "cv_resolve_batch",
     "cv_ed25519_dedupe_keys_device", "cv_ed25519_dedupe_keys_workspace",
@@ -207,6 +207,12 @@ def load():
         lib.cv_uniq_lookup.restype = ctypes.c_int
         lib.cv_uniq_load.argtypes = [_vp, _sz] + [_vp] * 4
         lib.cv_uniq_load.restype = ctypes.c_int
+        lib.cv_uniq_snapshot.argtypes = [_vp, _vp, _sz] + [_vp] * 5
+        lib.cv_uniq_snapshot.restype = ctypes.c_int
+        lib.cv_uniq_clear.argtypes = [_vp]
+        lib.cv_uniq_clear.restype = ctypes.c_int
+        lib.cv_uniq_install.argtypes = [_vp, _sz] + [_vp] * 4
+        lib.cv_uniq_install.restype = ctypes.c_int
         lib.cv_uniq_set_max_rounds.argtypes = [_vp, ctypes.c_int]
         lib.cv_uniq_set_max_rounds.restype = ctypes.c_int
         lib.cv_uniq_stats.argtypes = [_vp, _vp, _sz]
@@ -1132,6 +1138,52 @@ class UniquenessSet:
             raise ValueError("one id, index and caller per key")
         _check(self._lib.cv_uniq_load(h, n, _p(state_key), _p(consumed_id), _p(consumed_index), _p(consumed_caller)),
                "cv_uniq_load")
+
+    def snapshot_chunks(self, max_entries: int):
+        """One pass of cv_uniq_snapshot (DistributedImmutableMap.snapshot) as a generator of (state_key (k,32) u8,
+        consumed_id (k,32) u8, consumed_index u32[k], consumed_caller u32[k]) chunks of at most max_entries records,
+        in the table's slot order; chunks may be empty.  A call that changes the set between two chunks ends the pass
+        with CvError -3."""
+        m = int(max_entries)
+        if m < 1:
+            raise ValueError("max_entries must be at least 1")
+        cursor = np.zeros(2, np.uint64)
+        key, cid = np.zeros((m, 32), np.uint8), np.zeros((m, 32), np.uint8)
+        cix, cc = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        n = _sz(0)
+        while int(cursor[0]) != 0xFFFFFFFFFFFFFFFF:
+            _check(self._lib.cv_uniq_snapshot(self._open(), _p(cursor), m, _p(key), _p(cid), _p(cix), _p(cc),
+                                              ctypes.byref(n)), "cv_uniq_snapshot")
+            k = n.value
+            yield key[:k].copy(), cid[:k].copy(), cix[:k].copy(), cc[:k].copy()
+
+    def snapshot(self, max_entries=None):
+        """Every entry of the set: (state_key (n,32) u8, consumed_id (n,32) u8, consumed_index u32[n], consumed_caller
+        u32[n]) of one whole pass, in the table's slot order.  max_entries: the records per call of a chunked pass
+        (default: room for every resident entry)."""
+        m = max(self.stats()["resident"], 1) if max_entries is None else int(max_entries)
+        parts = list(self.snapshot_chunks(m))
+        if not parts:
+            return np.zeros((0, 32), np.uint8), np.zeros((0, 32), np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        return tuple(np.concatenate([p[j] for p in parts]) for j in range(4))
+
+    def clear(self):
+        """cv_uniq_clear (map.clear()): the set is empty afterwards; capacity and slots are kept."""
+        _check(self._lib.cv_uniq_clear(self._open()), "cv_uniq_clear")
+
+    def install(self, state_key, consumed_id, consumed_index, consumed_caller):
+        """cv_uniq_install (DistributedImmutableMap.install): the set holds exactly these n entries afterwards;
+        CvError -3 with the set unchanged if a key repeats."""
+        h = self._open()
+        state_key = _u8(state_key)
+        consumed_id = _u8(consumed_id)
+        n = state_key.size // 32
+        consumed_index = np.ascontiguousarray(consumed_index, dtype=np.uint32)
+        consumed_caller = np.ascontiguousarray(consumed_caller, dtype=np.uint32)
+        if consumed_id.size != 32 * n or consumed_index.shape[0] != n or consumed_caller.shape[0] != n:
+            raise ValueError("one id, index and caller per key")
+        _check(self._lib.cv_uniq_install(h, n, _p(state_key), _p(consumed_id), _p(consumed_index), _p(consumed_caller)),
+               "cv_uniq_install")
 
     def reserve(self, capacity: int):
         _check(self._lib.cv_uniq_reserve(self._open(), int(capacity)), "cv_uniq_reserve")

@@ -17,6 +17,8 @@ transaction — one lock acquisition and one durable commit (fsync) per batch in
 transaction.  Each result is None (committed) or the UniquenessConflict the sequential call would
 have raised.  DeviceUniquenessProvider makes the same decisions on the GPU: the device-resident set of
 include/cordaverify.h (cv_uniq), one call per batch, optionally with the persistent provider as its durable log.
+Its snapshot() / install() are DistributedImmutableMap's (the Raft notary's state machine, corda_amd/raft.py): a
+Snapshot carries the set's entries and the party table, and goes to a file and back.
 
 The node's JDBC/H2 store is out of scope; the persistent provider keeps the
 reference's table and columns on SQLite (Python's sqlite3, synchronous=FULL, WAL journal), keyed by
@@ -226,6 +228,82 @@ class PersistentUniquenessProvider:
             raise UniquenessException(c)
 
 
+@dataclass(eq=False)
+class Snapshot:
+    """The contents of a DeviceUniquenessProvider at one moment: the party table and the four arrays of
+    native.UniquenessSet.snapshot (state_key (n,32) u8, consumed_id (n,32) u8, consumed_index u32[n], consumed_caller
+    u32[n]).  consumed_caller holds handles into `parties`, so the arrays mean nothing without the table.
+
+    write / read: one file — magic "CVUSNAP1", u32 version, u32 flags (bit 0: leaf_keys), u64 entries, u32 parties;
+    each party name as u32 length + UTF-8; the four arrays, little-endian, in the order above; the SHA-256 of
+    everything before it.  read refuses a file whose trailer, magic, version or length is wrong."""
+    parties: List[str]
+    state_key: np.ndarray
+    consumed_id: np.ndarray
+    consumed_index: np.ndarray
+    consumed_caller: np.ndarray
+    leaf_keys: bool = False
+
+    MAGIC = b"CVUSNAP1"
+    VERSION = 1
+
+    def __len__(self) -> int:
+        return int(self.consumed_index.shape[0])
+
+    def arrays(self):
+        return self.state_key, self.consumed_id, self.consumed_index, self.consumed_caller
+
+    def to_bytes(self) -> bytes:
+        n = len(self)
+        names = [p.encode() for p in self.parties]
+        body = b"".join([self.MAGIC, struct.pack("<IIQI", self.VERSION, 1 if self.leaf_keys else 0, n, len(names)),
+                         b"".join(struct.pack("<I", len(b)) + b for b in names),
+                         np.ascontiguousarray(self.state_key, np.uint8).tobytes(),
+                         np.ascontiguousarray(self.consumed_id, np.uint8).tobytes(),
+                         np.ascontiguousarray(self.consumed_index, "<u4").tobytes(),
+                         np.ascontiguousarray(self.consumed_caller, "<u4").tobytes()])
+        return body + hashlib.sha256(body).digest()
+
+    @classmethod
+    def from_bytes(cls, raw: bytes) -> "Snapshot":
+        bad = IllegalArgumentException
+        if len(raw) < len(cls.MAGIC) + 20 + 32 or raw[:8] != cls.MAGIC:
+            raise bad("not a uniqueness snapshot")
+        if hashlib.sha256(raw[:-32]).digest() != raw[-32:]:
+            raise bad("uniqueness snapshot: the SHA-256 trailer does not match")
+        version, flags, n, nparties = struct.unpack_from("<IIQI", raw, 8)
+        if version != cls.VERSION:
+            raise bad(f"uniqueness snapshot: version {version}")
+        p, end = 28, len(raw) - 32
+        parties = []
+        for _ in range(nparties):
+            if p + 4 > end:
+                raise bad("uniqueness snapshot: truncated party table")
+            (m,) = struct.unpack_from("<I", raw, p)
+            if p + 4 + m > end:
+                raise bad("uniqueness snapshot: truncated party table")
+            parties.append(raw[p + 4:p + 4 + m].decode())
+            p += 4 + m
+        if end - p != 72 * n:
+            raise bad("uniqueness snapshot: the arrays do not fill the file")
+        key = np.frombuffer(raw, np.uint8, 32 * n, p).reshape(n, 32).copy()
+        cid = np.frombuffer(raw, np.uint8, 32 * n, p + 32 * n).reshape(n, 32).copy()
+        cix = np.frombuffer(raw, "<u4", n, p + 64 * n).astype(np.uint32)
+        cc = np.frombuffer(raw, "<u4", n, p + 68 * n).astype(np.uint32)
+        if n and int(cc.max()) >= nparties:
+            raise bad("uniqueness snapshot: a caller handle past the party table")
+        return cls(parties, key, cid, cix, cc, bool(flags & 1))
+
+    def write(self, path: str) -> None:
+        with open(path, "wb") as f:
+            f.write(self.to_bytes())
+
+    @classmethod
+    def read(cls, path: str) -> "Snapshot":
+        with open(path, "rb") as f:
+            return cls.from_bytes(f.read())
+
+
 class DeviceUniquenessProvider:
     """The commit step on the device: a native.UniquenessSet (cv_uniq, include/cordaverify.h) behind the interface
     of the two providers above.  A batch is decided in ONE call, exactly as InMemoryUniquenessProvider.commit_batch
@@ -334,6 +412,28 @@ class DeviceUniquenessProvider:
 
     def __len__(self) -> int:
         return self._set.stats()["resident"]
+
+    def snapshot(self, max_entries: Optional[int] = None) -> Snapshot:
+        """DistributedImmutableMap.snapshot (DistributedImmutableMap.kt:87-92): every entry of the set with the party
+        table its caller handles index, read out of device memory in one pass (chunked when max_entries is given)."""
+        with self._lock:
+            key, cid, cix, cc = self._set.snapshot(max_entries)
+            return Snapshot(list(self._parties), key, cid, cix, cc, self.leaf_keys)
+
+    def install(self, snapshot: Snapshot) -> None:
+        """DistributedImmutableMap.install (DistributedImmutableMap.kt:95-105): the set's contents and the party
+        table become the snapshot's.  A provider with a log keeps to its log: the set stores key hashes, not the state
+        references the log's rows are keyed by, so a log cannot be rebuilt from a snapshot."""
+        if self._log is not None:
+            raise IllegalArgumentException("install: this provider is warmed from its commit log")
+        if bool(snapshot.leaf_keys) != self.leaf_keys:
+            raise IllegalArgumentException("install: the snapshot's keys are of the other kind (leaf_keys)")
+        if len(snapshot) and int(snapshot.consumed_caller.max()) >= len(snapshot.parties):
+            raise IllegalArgumentException("install: a caller handle past the party table")
+        with self._lock:
+            self._set.install(*snapshot.arrays())
+            self._parties = list(snapshot.parties)
+            self._handle = {name: h for h, name in enumerate(self._parties)}
 
     def get(self, state) -> Optional[ConsumingTx]:
         with self._lock:

@@ -50,6 +50,10 @@
  *                                 InMemoryUniquenessProvider.kt:14-36 decides it (the decision half of
  *                                 PersistentUniquenessProvider.kt:61-81), for NotaryFlow.kt:133-141: a device-resident
  *                                 set of consumed states, a batch decided exactly as sequential commits would
+ *   cv_uniq_snapshot +             DistributedImmutableMap.snapshot / install
+ *   cv_uniq_install               node/src/main/kotlin/net/corda/node/services/transactions/DistributedImmutableMap.kt:
+ *                                 87-105, the state machine of RaftUniquenessProvider.kt:44-129: the set's entries
+ *                                 read out in chunks, and a set that takes over a snapshot's contents in one step
  *   cv_missing_signers        N x  SignedTransaction.getMissingSignatures() and the verdict verifySignatures draws from it
  *                                 core/src/main/kotlin/net/corda/core/transactions/SignedTransaction.kt:58-72,89-93
  *                                 (tx.mustSign.filter { !it.isFulfilledBy(sigKeys) } minus allowedToBeMissing) over
@@ -337,13 +341,15 @@ int cv_ed25519_sign_keyed(cv_ctx *ctx, const cv_signer *s, size_t n, const uint8
  * choice is SecureHash.sha256 of the serialised StateRef (Structures.kt:337), the input's Merkle leaf hash.
  *   - Open addressing over a power-of-two slot count of at least 2 x capacity (16 at the least), about 76 bytes a
  *     slot.  Slots are chosen by a hash of the whole key mixed with a per-set random seed, never by key bits: keys
- *     are SHA-256 outputs a submitter can grind.  Nothing is deleted.
+ *     are SHA-256 outputs a submitter can grind.  No single entry is deleted; cv_uniq_clear and cv_uniq_install
+ *     replace the whole contents.
  *   - A call that would take the set past its capacity (resident + the call's states, repeats included) returns
  *     CV_E_OOM before any change to the set and before any output is written; cv_uniq_reserve makes room (a rehash
  *     on the device into a larger table; it never shrinks).
  *   - Calls on one set serialise on a mutex in the set (the reference's ThreadBox); all are synchronous.  The set
  *     has a stream and a workspace of its own, so it runs beside the context's other calls.  It is not durable: a
- *     restarted notary warms it with cv_uniq_load from its commit log.
+ *     restarted notary warms it with cv_uniq_load from its commit log, or with cv_uniq_install from a snapshot
+ *     (cv_uniq_snapshot) that it or another replica wrote.
  *   - More than 0xfffffffe requests, states or keys: CV_E_TOO_LARGE; so is a capacity, or one call, of more than
  *     2^30 states.  A count of 0 returns CV_OK and touches nothing.  cv_uniq_close(NULL) is a no-op; a set is
  *     closed before its context. */
@@ -385,6 +391,41 @@ int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key /* n*32 */, ui
  * otherwise CV_E_ARGS, the set unchanged (the check runs on the device before the first insert). */
 int cv_uniq_load(cv_uniq *u, size_t n, const uint8_t *state_key /* n*32 */, const uint8_t *consumed_id /* n*32 */,
                  const uint32_t *consumed_index /* n */, const uint32_t *consumed_caller /* n */);
+
+/* DistributedImmutableMap.snapshot (node/src/main/kotlin/net/corda/node/services/transactions/
+ * DistributedImmutableMap.kt:87-92: every entry written out), in chunks of at most max_entries records: record j of a
+ * call is (state_key[j], consumed_id[j], consumed_index[j], consumed_caller[j]), byte for byte what was committed.
+ *   - cursor is opaque.  {0, 0} starts a pass; each call advances it; after the call that delivers the last entries
+ *     cursor[0] == UINT64_MAX.  A call with such a finished cursor returns CV_OK with *n = 0 and writes no record.
+ *   - A call writes *n <= max_entries records, and of the four arrays only the *n entries used: nothing before or
+ *     behind them.  *n may be 0 on a call that is not the last (a stretch of empty slots): loop on the cursor, not on
+ *     *n.  One call looks at max(2 * max_entries, 65,536) slots of the table at the most (2 x: the table is at most
+ *     half full), so a pass with a small buffer takes about resident / max_entries calls.
+ *   - Over one pass every resident entry is reported exactly once, within a call in ascending slot order.  Two passes
+ *     over an unchanged set are byte-identical.  The order is the table's, not the order of commitment.
+ *   - The set keeps an epoch that every call advances which may change the table's contents or layout:
+ *     cv_uniq_commit_batch and cv_notarise_batch (also when they accepted nothing), cv_uniq_load, cv_uniq_install,
+ *     cv_uniq_clear, and a cv_uniq_reserve that rehashes.  The cursor carries the epoch of the call that started the
+ *     pass; continuing a pass after the epoch moved, or with a cursor no pass of this set gave, returns CV_E_ARGS and
+ *     writes nothing: a torn snapshot is refused.  Lookup, stats and snapshot leave the epoch alone.
+ *   - max_entries == 0 or a NULL cursor, n or array: CV_E_ARGS.  max_entries above 2^30: CV_E_TOO_LARGE.  A failed
+ *     call writes nothing, *n and the cursor included. */
+int cv_uniq_snapshot(cv_uniq *u, uint64_t cursor[2], size_t max_entries, uint8_t *state_key /* max_entries*32 */,
+                     uint8_t *consumed_id /* max_entries*32 */, uint32_t *consumed_index /* max_entries */,
+                     uint32_t *consumed_caller /* max_entries */, size_t *n);
+
+/* map.clear() (DistributedImmutableMap.kt:98): afterwards the set is empty, CV_UNIQ_STAT_RESIDENT is 0, every key is
+ * absent and may be committed again.  Capacity and slot count are kept. */
+int cv_uniq_clear(cv_uniq *u);
+
+/* DistributedImmutableMap.install (DistributedImmutableMap.kt:95-105): map.clear(), then put every entry of a
+ * snapshot, as ONE step: afterwards the set holds exactly the n given entries, whatever it held before.  The new
+ * contents are built in a fresh table beside the old one, which is swapped in on success, so a failed call leaves the
+ * set exactly as it was: a key repeated within the call is CV_E_ARGS, n above 2^30 CV_E_TOO_LARGE, no memory for the
+ * second table CV_E_OOM.  n == 0 is cv_uniq_clear.  The capacity becomes max(capacity, n); it never shrinks.  A Raft
+ * state machine calls it from its one writer thread (Copycat's state machine thread). */
+int cv_uniq_install(cv_uniq *u, size_t n, const uint8_t *state_key /* n*32 */, const uint8_t *consumed_id /* n*32 */,
+                    const uint32_t *consumed_index /* n */, const uint32_t *consumed_caller /* n */);
 
 /* The parallel decision rounds a commit runs at the most before one lane decides the requests still open in order
  * (0 = that serial tail only; at the most 64; default 8).  A batch without conflicts needs one round, a chain of k
