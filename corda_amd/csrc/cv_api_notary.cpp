@@ -149,7 +149,7 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(base, h, in_bytes, hipMemcpyHostToDevice, s));
     // the key dedupe ahead of the Merkle kernels; its count and keys come back through the outputs' pinned block
-    CV_TRY(fk.enqueue(base, base + i_pk, key_seed(1) | 1, u->nout.p, s));
+    CV_TRY(fk.enqueue(base, base + i_pk, key_seed(1) | 1, u->nout.p, s, base + i_sig, base + w_voff, base + w_vlen));
 
     uint32_t *const d_llen = at<uint32_t>(base, i_llen), *const d_txb = at<uint32_t>(base, i_txb);
     uint32_t *const d_tsb = at<uint32_t>(base, i_tsb), *const d_ldig = at<uint32_t>(base, w_ldig);
@@ -176,7 +176,11 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
             size_t nkeys = 0;
             rc = fk.decide(u->nout.p, &nkeys);
             if (rc != CV_OK) return rc;
-            if (nkeys) {
+            if (fk.hot) {
+                Device &d = *find_dev(ctx, u->ordinal);
+                std::lock_guard<std::mutex> gd(d.mu);
+                rc = fk.verify_hot(ctx, d, u->nout.p, base + o_ids, d_bm, base + w_sst, s);
+            } else if (nkeys) {
                 // the key pool is the device's: its lock inside the set's, as the unkeyed call below takes it
                 Device &d = *find_dev(ctx, u->ordinal);
                 std::lock_guard<std::mutex> gd(d.mu);

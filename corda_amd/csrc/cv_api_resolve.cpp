@@ -157,7 +157,7 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_
         CV_TRY(hipMemcpyAsync(base, h, in_bytes, hipMemcpyHostToDevice, s));
         CV_TRY(clk.mark(1, s));
         // the key dedupe ahead of the Merkle kernels; its count and keys come back through the outputs' pinned block
-        CV_TRY(fk.enqueue(base, base + i_pk, seed, d.ts_out.p, s));
+        CV_TRY(fk.enqueue(base, base + i_pk, seed, d.ts_out.p, s, base + i_sig, base + w_voff, base + w_vlen));
 
         uint32_t *const d_llen = at<uint32_t>(base, i_llen), *const d_txb = at<uint32_t>(base, i_txb);
         uint32_t *const d_tsb = at<uint32_t>(base, i_tsb), *const d_ldig = at<uint32_t>(base, w_ldig);
@@ -187,7 +187,10 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, uint64_
             size_t nkeys = 0;
             int rc = fk.decide(d.ts_out.p, &nkeys);
             if (rc != CV_OK) return rc;
-            if (nkeys) {
+            if (fk.hot) {
+                rc = fk.verify_hot(ctx, d, d.ts_out.p, base + o_ids, at<uint64_t>(base, w_bm), base + w_sst, s);
+                if (rc != CV_OK) return rc;
+            } else if (nkeys) {
                 rc = verify_keyed_locked(ctx, d, N, nkeys, fk.host_keys(d.ts_out.p), base + fk.keys,
                                          at<uint32_t>(base, fk.kidx), base + i_sig, base + o_ids, at<uint64_t>(base, w_voff),
                                          at<uint32_t>(base, w_vlen), at<uint64_t>(base, w_bm), base + w_sst, s, nullptr);

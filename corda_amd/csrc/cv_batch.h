@@ -99,16 +99,33 @@ template <class F> inline int dispatch_one(cv_ctx *ctx, size_t n, F fn) {
 //   decide   before the verify: waits for the event — the one synchronisation the route adds; the kernels enqueued
 //            since run meanwhile — and gives the distinct keys when the call takes the keyed path, 0 when it stays
 //            unkeyed (more keys than rows), CV_E_HIP after a probe error
+// Modes 3 and 4 are the hot-key route (cv_hotkeys.h) in the same three places: plan takes the route's
+// workspace as one piece (mode 3: more than the tri-chain size, hot_min 8; mode 4: any batch, hot_min 2), enqueue runs
+// hotkeys_front (the read-back is head | the hot key rows only), decide waits for it and leaves the keyed count 0, and
+// the call hands its verify to verify_hot — verify_hotkeys_locked — in place of the two branches, behind
+// cvk_tx_sig_refs, whose message references the record gather copies.
 struct FusedKeyed {
-    bool want = false;
+    bool want = false, hot = false;
     size_t n = 0, rows = 0, head = 0, keys = 0, kidx = 0, ws = 0;
     CvdLayout L{};
+    CvhLayout HL{};
+    CvHot H{};
+    uint32_t hot_min = 0, hot_cap = 0;
     hipEvent_t ev = nullptr;
     ~FusedKeyed() {
         if (ev) (void)hipEventDestroy(ev);
     }
     void plan(const Opts &o, uint32_t key_cap, size_t nsig, Layout &lay) {
         n = nsig;
+        if (o.fused_keyed >= 3) {
+            hot_min = o.fused_keyed == 4 ? 2 : CVH_HOT_MIN_DEFAULT, hot_cap = key_cap;
+            rows = (size_t)cvh_rows(n, hot_min, hot_cap);
+            want = hot = rows != 0 && (o.fused_keyed == 4 || n > o.plan.tri_max);
+            if (!want) return;
+            HL = cvh_layout(n);
+            ws = lay.take((size_t)HL.bytes);
+            return;
+        }
         rows = std::min<size_t>(o.fused_keyed == 2 ? n : n / 8, key_cap);
         want = rows != 0 && (o.fused_keyed == 2 || (o.fused_keyed == 1 && n > o.plan.tri_max));
         if (!want) return;
@@ -116,8 +133,17 @@ struct FusedKeyed {
         head = lay.take(16), keys = lay.take(32 * n), kidx = lay.take(4 * n), ws = lay.take((size_t)L.bytes);
     }
     size_t pinned_bytes() const { return want ? 16 + 32 * rows : 0; }
-    hipError_t enqueue(uint8_t *base, const uint8_t *d_pk, uint64_t seed, void *pin, hipStream_t s) {
+    // d_sig, d_off, d_len: the records the hot-key route gathers (d_off / d_len may be written later on the stream)
+    hipError_t enqueue(uint8_t *base, const uint8_t *d_pk, uint64_t seed, void *pin, hipStream_t s,
+                       const void *d_sig = nullptr, const void *d_off = nullptr, const void *d_len = nullptr) {
         if (!want) return hipSuccess;
+        if (hot) {
+            H = cvh_args(n, hot_min, hot_cap, d_pk, d_sig, d_off, d_len, base + ws, HL);
+            hipError_t e = hotkeys_front(H, HL, base + ws, seed, rows, pin, s);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (e == hipSuccess) e = hipEventRecord(ev, s);
+            return e;
+        }
         const CvDedupe D = cvd_args(n, d_pk, base + keys, base + kidx, base + head, base + ws, seed, L);
         uint32_t *sums[CVD_LEVELS];
         for (int k = 0; k < CVD_LEVELS; k++) sums[k] = at<uint32_t>(base, ws + (size_t)L.sum[k]);
@@ -131,10 +157,16 @@ struct FusedKeyed {
         *nkeys = 0;
         if (!want) return CV_OK;
         CV_TRY(hipEventSynchronize(ev));
+        if (hot) return CV_OK;
         const uint32_t nk = *static_cast<const uint32_t *>(pin);
         if (nk == 0 || nk > n) return CV_E_HIP;
         if (nk <= rows) *nkeys = nk;
         return CV_OK;
+    }
+    // the call's verify under modes 3 and 4, after decide; the caller holds d.mu
+    int verify_hot(cv_ctx *ctx, Device &d, const void *pin, const uint8_t *arena, uint64_t *bitmap, uint8_t *status,
+                   hipStream_t s) const {
+        return verify_hotkeys_locked(ctx, d, H, rows, pin, arena, bitmap, status, s, nullptr);
     }
     const uint8_t *host_keys(const void *pin) const { return static_cast<const uint8_t *>(pin) + 16; }
 };

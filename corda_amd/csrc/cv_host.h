@@ -347,7 +347,7 @@ inline const OptDesc kOpt[CV_OPT_COUNT] = {
     {1, 1, 16},                         // CV_OPT_MID_PIECES
     {2, 2, 4},                          // CV_OPT_PIPE_SLOTS
     {2, 0, 2},                          // CV_OPT_TXS_MERKLE_STREAM
-    {0, 0, 2},                          // CV_OPT_FUSED_KEYED (auto lost to the parent in the measurement of DESIGN.md §5.14)
+    {0, 0, 4},                          // CV_OPT_FUSED_KEYED (auto lost to the parent in the measurement of DESIGN.md §5.14)
 };
 
 // A snapshot of a context's options, taken once per call.
@@ -549,6 +549,18 @@ hipError_t verify_device_locked(cv_ctx *ctx, Device &d, size_t n, const uint8_t 
 int verify_keyed_locked(cv_ctx *ctx, Device &d, size_t n, size_t nkeys, const uint8_t *hkeys, const uint8_t *d_keys,
                         const uint32_t *d_key_index, const uint8_t *sig, const uint8_t *arena, const uint64_t *off,
                         const uint32_t *len, uint64_t *bitmap, uint8_t *status, hipStream_t s, float *phase_ms);
+// cv_api_hotkeys.cpp: the hot-key route (cv_hotkeys.h) in its two halves, for cv_ed25519_verify_device_hotkeys and the
+// fused batch calls.  hotkeys_front enqueues on s the dedupe over H.pk, the route's steps up to the records' scan and
+// the copy of head | `rows` hot key rows (cvh_rows) to `host`; it takes no lock and synchronises nothing.  Once that
+// copy has arrived — the route's one synchronisation, the caller's — verify_hotkeys_locked decides from it and
+// enqueues the rest: verify_device_locked over the caller's arrays when no key is hot, verify_keyed_locked over them
+// when every key is, else the gather (it reads H.off / H.len: behind whatever writes them), both over their
+// sub-batches and the merge into bitmap / status (optional).  route_out (optional) = {nkeys, hot keys, hot records,
+// cold records}.  The caller holds d.mu; CV_E_HIP after a probe error of the dedupe.
+hipError_t hotkeys_front(const CvHot &H, const CvhLayout &L, void *ws, uint64_t seed, size_t rows, void *host,
+                         hipStream_t s);
+int verify_hotkeys_locked(cv_ctx *ctx, Device &d, const CvHot &H, size_t rows, const void *host, const uint8_t *arena,
+                          uint64_t *bitmap, uint8_t *status, hipStream_t s, uint32_t route_out[4]);
 
 inline Device *find_dev(cv_ctx *ctx, int device) {
     for (auto &d : ctx->devs)

@@ -14,6 +14,7 @@
 //   cv_k_tearoff.hip the tear-off verifier and the oracle's signing step (cv_tearoff.h): check bytes, gate, compaction
 //   cv_k_resolve.hip the graph steps of cv_resolve_batch (cv_resolve.h): join-table insert, probe, gate
 //   cv_k_dedupe.hip  the device key dedupe (cv_keydedupe.h): insert, mark, count, scan, emit
+//   cv_k_hotkeys.hip the hot-key route (cv_hotkeys.h): tally, classify, keys, flag, gather, merge
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,6 +28,7 @@
 #include "cv_tearoff.h"
 #include "cv_resolve.h"
 #include "cv_keydedupe.h"
+#include "cv_hotkeys.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -211,6 +213,13 @@ __global__ void cv_dedupe_mark_kernel(CvDedupe D);
 __global__ void cv_dedupe_emit_kernel(CvDedupe D);
 __global__ void cv_dedupe_count_kernel(uint32_t m, const uint32_t *arr, uint32_t *sums);
 __global__ void cv_dedupe_scan_kernel(uint32_t m, uint32_t *arr, const uint32_t *base, uint32_t *total);
+// the hot-key route (cv_k_hotkeys.hip, cv_hotkeys.h); its compactions are the dedupe's count and scan kernels
+__global__ void cv_hot_tally_kernel(CvHot H);
+__global__ void cv_hot_classify_kernel(CvHot H);
+__global__ void cv_hot_keys_kernel(CvHot H);
+__global__ void cv_hot_flag_kernel(CvHot H);
+__global__ void cv_hot_gather_kernel(CvHot H);
+__global__ void cv_hot_merge_kernel(CvHot H, uint64_t *bitmap, uint8_t *status);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

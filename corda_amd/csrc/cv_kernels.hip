@@ -508,6 +508,35 @@ hipError_t cvk_dedupe(const CvDedupe *D, uint32_t *const *sums, hipStream_t stre
     return hipGetLastError();
 }
 
+// ---- the hot-key route (cv_hotkeys.h), behind cvk_dedupe on the same stream.  front: the counters zeroed, tally,
+// classify, the compaction of the candidates, the classes and hot key rows, the records' flags and their compaction —
+// all the host reads back (head | hot_keys).  sums: the dedupe's block sums, free again once its scan has run.
+hipError_t cvk_hotkeys_front(const CvHot *H, uint32_t *const *sums, hipStream_t stream) {
+    if (!H || H->n == 0 || H->hot_min == 0 || !sums) return hipErrorInvalidValue;
+    const hipError_t e = hipMemsetAsync(H->count, 0, 4 * (size_t)H->n, stream);
+    if (e != hipSuccess) return e;
+    const dim3 grid = uniq_grid(H->n), block(CV_BLOCK);
+    hipLaunchKernelGGL(cv_hot_tally_kernel, grid, block, 0, stream, *H);
+    hipLaunchKernelGGL(cv_hot_classify_kernel, grid, block, 0, stream, *H);
+    dedupe_scan(H->n, H->cand, sums, H->stat + CVH_STAT_CAND, stream);
+    hipLaunchKernelGGL(cv_hot_keys_kernel, grid, block, 0, stream, *H);
+    hipLaunchKernelGGL(cv_hot_flag_kernel, grid, block, 0, stream, *H);
+    dedupe_scan(H->n, H->rank, sums, H->head + CVH_HEAD_NHOT, stream);
+    return hipGetLastError();
+}
+
+hipError_t cvk_hotkeys_gather(const CvHot *H, hipStream_t stream) {
+    if (!H || H->n == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_hot_gather_kernel, uniq_grid(H->n), dim3(CV_BLOCK), 0, stream, *H);
+    return hipGetLastError();
+}
+
+hipError_t cvk_hotkeys_merge(const CvHot *H, uint64_t *bitmap, uint8_t *status, hipStream_t stream) {
+    if (!H || H->n == 0 || !bitmap) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_hot_merge_kernel, uniq_grid(H->n), dim3(CV_BLOCK), 0, stream, *H, bitmap, status);
+    return hipGetLastError();
+}
+
 // The snapshot of a window of the uniqueness set (cv_uniq.h): count, the scan of the block totals (the dedupe's, which
 // also writes the window's total) and emit.  sums: CVD_LEVELS arrays, the first of one word per CV_BLOCK slots of the
 // window, each next of one word per CVD_SPAN words of the one before.

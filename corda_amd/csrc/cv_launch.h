@@ -8,6 +8,7 @@
 #include "cv_notary.h"
 #include "cv_tearoff.h"
 #include "cv_keydedupe.h"
+#include "cv_hotkeys.h"
 #include "cv_resolve.h"
 #include "cv_uniq.h"
 
@@ -133,6 +134,16 @@ hipError_t cvk_resolve_gate(const CvResolve *R, hipStream_t stream);
 // D->key_index[n], *D->nkeys (CVD_NONE after a probe error).  D->stat lies directly behind D->tab (cvd_layout) and
 // sums[CVD_LEVELS] are the levels' block sums; the workspace needs no preparation.  1 <= n <= 0xfffffffe.
 hipError_t cvk_dedupe(const CvDedupe *D, uint32_t *const *sums, hipStream_t stream);
+// The hot-key route (cv_hotkeys.h; kernels in cv_k_hotkeys.hip), every step enqueued on `stream`, nothing synchronised.
+//   front : behind cvk_dedupe over the same keys — the counters zeroed, tally, classify, the candidates' compaction, the
+//           classes and hot key rows, the records' flags and their compaction -> H->head | H->hot_keys, what the host
+//           reads back; sums: the dedupe's block sums (used one compaction after another).  H->hot_min >= 1.
+//   gather: the stable partition of the records into H->g_* and H->perm (reads H->off / H->len: behind whatever
+//           writes them)
+//   merge : behind the two sub-batch verifies -> bitmap (ceil(n / 64) words, zero tail bits), status (optional)
+hipError_t cvk_hotkeys_front(const CvHot *H, uint32_t *const *sums, hipStream_t stream);
+hipError_t cvk_hotkeys_gather(const CvHot *H, hipStream_t stream);
+hipError_t cvk_hotkeys_merge(const CvHot *H, uint64_t *bitmap, uint8_t *status, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

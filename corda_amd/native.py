@@ -73,6 +73,7 @@ EXPORTED = (
     "cv_missing_signers", "cv_missing_signers_workspace", "cv_missing_signers_device",
     "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch", "cv_resolve_batch",
     "cv_ed25519_dedupe_keys_device", "cv_ed25519_dedupe_keys_workspace",
+    "cv_ed25519_verify_device_hotkeys", "cv_ed25519_verify_hotkeys_workspace",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -255,6 +256,12 @@ def load():
             lib.cv_ed25519_dedupe_keys_device.restype = ctypes.c_int
             lib.cv_ed25519_dedupe_keys_workspace.argtypes = [_sz]
             lib.cv_ed25519_dedupe_keys_workspace.restype = ctypes.c_uint64
+        if hasattr(lib, "cv_ed25519_verify_device_hotkeys"):
+            lib.cv_ed25519_verify_device_hotkeys.argtypes = [_vp, ctypes.c_int, _sz] + [_vp] * 7 + [ctypes.c_uint32, _vp, _vp,
+                                                                                                  _vp]
+            lib.cv_ed25519_verify_device_hotkeys.restype = ctypes.c_int
+            lib.cv_ed25519_verify_hotkeys_workspace.argtypes = [_sz]
+            lib.cv_ed25519_verify_hotkeys_workspace.restype = ctypes.c_uint64
         lib.cv_calibrate.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         lib.cv_calibrate.restype = ctypes.c_int
         lib.cv_calibrate_cycles.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -951,6 +958,19 @@ class Engine:
                                                        d_key_index or None, d_nkeys or None, d_workspace or None,
                                                        stream or None), "cv_ed25519_dedupe_keys_device")
 
+    def verify_device_hotkeys(self, device: int, n: int, d_pk: int, d_sig: int, d_arena: int, d_off: int, d_len: int,
+                              d_bitmap: int, d_status: int, d_workspace: int, hot_min: int = 0, stream: int = 0) -> dict:
+        """The hot-key route over device arrays (cv_ed25519_verify_device_hotkeys): the records of keys that occur at
+        least hot_min times (0: 8) through the keyed path, the rest through the unkeyed one; d_bitmap and d_status
+        (0: none) as verify_device writes them.  d_workspace of verify_hotkeys_workspace(n) bytes.  Synchronises the
+        stream once, enqueues the verifies and returns the split: nkeys, hot_keys, hot, cold."""
+        route = (ctypes.c_uint32 * 4)()
+        _check(self._lib.cv_ed25519_verify_device_hotkeys(self._h, device, n, d_pk or None, d_sig or None, d_arena or None,
+                                                          d_off or None, d_len or None, d_bitmap or None, d_status or None,
+                                                          hot_min, d_workspace or None, stream or None, route),
+               "cv_ed25519_verify_device_hotkeys")
+        return dict(nkeys=route[0], hot_keys=route[1], hot=route[2], cold=route[3])
+
     def sign_device(self, device: int, n: int, d_seed: int, d_arena: int, d_off: int, d_len: int, d_pk: int,
                     d_sig: int, stream: int = 0):
         _check(self._lib.cv_ed25519_sign_device(self._h, device, n, d_seed, d_arena, d_off, d_len, d_pk, d_sig,
@@ -1215,6 +1235,11 @@ def dedupe_keys(pk: np.ndarray):
 def dedupe_keys_workspace(n: int) -> int:
     """Bytes of device workspace Engine.dedupe_keys_device needs for n keys (host only)."""
     return int(load().cv_ed25519_dedupe_keys_workspace(n))
+
+
+def verify_hotkeys_workspace(n: int) -> int:
+    """Bytes of device workspace Engine.verify_device_hotkeys needs for n signatures (host only)."""
+    return int(load().cv_ed25519_verify_hotkeys_workspace(n))
 
 
 def tx_verdicts(bitmap: np.ndarray, tx_sig_begin) -> np.ndarray:

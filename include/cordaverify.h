@@ -840,6 +840,28 @@ int cv_ed25519_dedupe_keys_device(cv_ctx *ctx, int device, size_t n, const void 
                                   void *d_nkeys, void *d_workspace, void *stream);
 uint64_t cv_ed25519_dedupe_keys_workspace(size_t n);
 
+/* The hot-key route: N x PublicKey.verifyWithECDSA (CryptoUtilities.kt:90-96) for a batch whose keys
+ * are skewed — a few keys that sign thousands of records beside a long tail of keys seen once.  The batch is split on
+ * the device by how often each key occurs: the records of hot keys go through the keyed comb, the rest through the
+ * unkeyed path, and d_bitmap / d_status (optional) are, record for record, those of cv_ed25519_verify_device; inputs,
+ * alignment and outputs are that call's.  With the keys numbered in first-seen order (cv_ed25519_dedupe_keys_device), a
+ * key is a candidate iff it occurs at least hot_min times, and hot iff it is among the first cv_key_cache_reserve
+ * candidates in first-seen order (the pool never grows for this call; later candidates are cold).  hot_min 0 means 8;
+ * 1 makes every key hot up to the capacity; a value above n makes every record cold.  The classes depend on the input
+ * bytes alone.  d_workspace: cv_ed25519_verify_hotkeys_workspace(n) bytes, 16-byte aligned (overwritten; nothing is
+ * expected in it; it must stay untouched until the work on `stream` has finished).  route_out (host, optional) =
+ * {distinct keys, hot keys, hot records, cold records}.  The call synchronises `stream` ONCE, to read the hot key rows
+ * back (32 B each, resolved against the key pool as cv_ed25519_verify_device_keyed resolves its keys; cv_key_cache_stats
+ * counts one lookup per hot key row), then enqueues the rest and returns without synchronising again.  As for the
+ * keyed call, keyed calls on one device must share one stream.  n == 0 returns CV_OK and touches nothing;
+ * n > 0xfffffffe: CV_E_TOO_LARGE; a NULL ctx or required pointer: CV_E_ARGS — all before any device work.
+ * cv_ed25519_verify_hotkeys_workspace runs on the host and needs no device (0 for n > 0xfffffffe). */
+int cv_ed25519_verify_device_hotkeys(cv_ctx *ctx, int device, size_t n, const void *d_pk, const void *d_sig,
+                                     const void *d_arena, const void *d_off, const void *d_len, void *d_bitmap,
+                                     void *d_status /* optional */, uint32_t hot_min, void *d_workspace,
+                                     void *stream, uint32_t route_out[4] /* host, optional */);
+uint64_t cv_ed25519_verify_hotkeys_workspace(size_t n);
+
 int cv_ed25519_sign_device(cv_ctx *ctx, int device, size_t n, const void *d_seed, const void *d_arena,
                            const void *d_off, const void *d_len, void *d_pk, void *d_sig, void *stream);
 
@@ -928,8 +950,11 @@ int cv_calibrate_cycles(cv_ctx *ctx, int device, double *out);
 #define CV_OPT_FUSED_KEYED 23       /* cv_notarise_batch (validating) and cv_resolve_batch: the keyed verify path over the
                                        keys the device dedupe finds — 0 never, 1 auto (more than CV_OPT_TRI_MAX signatures,
                                        at least eight per distinct key, no more distinct keys than the key pool's
-                                       capacity), 2 whenever the distinct keys fit the pool's capacity.  Every output is
-                                       the same under all three.  Default 0: auto cost a resolve chain more than its keyed
+                                       capacity), 2 whenever the distinct keys fit the pool's capacity; 3 the hot-key
+                                       route (keys that occur at least 8 times keyed, the rest unkeyed)
+                                       for more than CV_OPT_TRI_MAX signatures, 4 the hot-key route for any batch with
+                                       keys that occur at least twice hot (tests at small shapes).  Every output is
+                                       the same under all five.  Default 0: auto cost a resolve chain more than its keyed
                                        verify saved */
 #define CV_OPT_COUNT 24
 int cv_set_option(cv_ctx *ctx, int option, int64_t value);
