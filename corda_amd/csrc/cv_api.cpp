@@ -2,7 +2,11 @@
 // (one lock, one persistent worker thread and a load count per device; batches routed whole to one device or cut
 // over several), verify workspace slots, the host-buffer pipeline (copy stream + input ring, direct DMA from pinned
 // buffers) for plain, keyed, Merkle and transaction batches with synchronous and asynchronous forms, tickets, the
-// device-resident verify and Merkle entry points used by bench.py, and calibration.  The engine state is
+// device-resident verify and Merkle entry points used by bench.py, and calibration.  The three pipelined calls
+// share one call frame (pipelined_call: shards, parts, error wait, ticket), one shard frame (shard_pipelined:
+// output, enqueue, ticket or finish) and one enqueue frame (PipeFrame: begin / stage / copied / launched / end,
+// draining when an enqueue function leaves early); pipe_enqueue, merkle_enqueue and txs_enqueue hold only what
+// differs: their sub-chunk plans and launch groups.  The engine state is
 // cv_host.h's, the staging logic cv_stage.h's; signing (cv_api_sign.cpp), partial Merkle trees (cv_api_pmt.cpp)
 // the uniqueness set (cv_api_uniq.cpp), missing signers (cv_api_ck.cpp), the notary's fused call (cv_api_notary.cpp),
 // the tear-off calls (cv_api_tearoff.cpp) and the resolve call (cv_api_resolve.cpp) are translation units of their own.
@@ -65,22 +69,36 @@ static hipError_t ensure_verify_ws(Slot &sl, size_t n) {
     return hipSuccess;
 }
 
+// One launch group on slot sl's workspace, stream s: ordered after the slot's previous group (ws_begin), its end
+// marked (ws_end) whether or not the launch succeeded; the launch's error comes first.
+template <class L>
+static hipError_t ws_run(Device &d, Slot &sl, hipStream_t s, L launch) {
+    hipError_t e = ws_begin(d, sl, s);
+    if (e != hipSuccess) return e;
+    e = launch();
+    const hipError_t e2 = ws_end(sl, s);
+    return e != hipSuccess ? e : e2;
+}
+
 // One verify launch group on slot sl, stream s.  split: the drain-overlap sub-chunks may be used.
 static hipError_t launch_verify(Device &d, const CvkPlan &plan, Slot &sl, uint32_t n, const uint8_t *pk,
                                 const uint8_t *sig, const uint8_t *arena, const uint64_t *off, const uint32_t *len,
                                 uint64_t *bitmap, uint8_t *status, hipStream_t s, hipEvent_t *ev, bool split,
                                 const CvkPrepOverlap *po = nullptr) {
-    hipError_t e = ensure_verify_ws(sl, n);
-    const hipStream_t prev = sl.last;
-    if (e == hipSuccess) e = ws_begin(d, sl, s);
-    // the helper stream writes the workspace too: it waits for the slot's previous user as s does
-    if (e == hipSuccess && po && prev && prev != s) e = hipStreamWaitEvent(po->aux, sl.ev, 0);
+    const hipError_t e = ensure_verify_ws(sl, n);
     if (e != hipSuccess) return e;
-    if (split && plan.split && n >= 131072) (void)slot_split(d, sl);   // without a helper the chunk runs whole
-    e = cvk_verify(&plan, n, pk, sig, arena, off, len, bitmap, status, sl.ws_tab.as<uint32_t>(), sl.ws_ok.as<uint8_t>(),
-                   sl.ws_dig.as<uint32_t>(), sl.ws_cap, s, ev, split && sl.split.s2 ? &sl.split : nullptr, po);
-    const hipError_t e2 = ws_end(sl, s);
-    return e != hipSuccess ? e : e2;
+    const hipStream_t prev = sl.last;
+    return ws_run(d, sl, s, [&] {
+        // the helper stream writes the workspace too: it waits for the slot's previous user as s does
+        if (po && prev && prev != s) {
+            const hipError_t ew = hipStreamWaitEvent(po->aux, sl.ev, 0);
+            if (ew != hipSuccess) return ew;
+        }
+        if (split && plan.split && n >= 131072) (void)slot_split(d, sl);   // without a helper the chunk runs whole
+        return cvk_verify(&plan, n, pk, sig, arena, off, len, bitmap, status, sl.ws_tab.as<uint32_t>(),
+                          sl.ws_ok.as<uint8_t>(), sl.ws_dig.as<uint32_t>(), sl.ws_cap, s, ev,
+                          split && sl.split.s2 ? &sl.split : nullptr, po);
+    });
 }
 
 // cv_ed25519_verify_device's launch group for a caller that already holds d.mu (cv_api_resolve.cpp, under dispatch_one)
@@ -527,11 +545,49 @@ struct VerifyIn {
     double t_entry = 0;   // host time the call entered the engine (CV_OPT_TIMELINE's host_pre)
 };
 
+// the arrays of a plain (per-record keys) call
+static VerifyIn verify_in(const uint8_t *pk, const uint8_t *sig, const uint8_t *arena, const uint64_t *off,
+                          const uint32_t *len, uint64_t *bitmap, uint8_t *status) {
+    VerifyIn in;
+    in.pk = pk;
+    in.sig = sig;
+    in.arena = arena;
+    in.off = off;
+    in.len = len;
+    in.bitmap = bitmap;
+    in.status = status;
+    return in;
+}
+
+// Where the verdicts of n records lie in a device (or pinned) output block: bitmap words | status bytes.
+struct VerdictOut {
+    size_t words, o_st, total_out;
+    explicit VerdictOut(size_t n) : words((n + 63) / 64), o_st(al16(words * 8)), total_out(o_st + al16(n)) {}
+};
+
 // A finished small-path call's host phases t[0..5] into the context's sums (cv_diag_stats CV_STATS_SMALL).
 static void small_account(cv_ctx *ctx, const double *t) {
     std::lock_guard<std::mutex> g(ctx->st_mu);
     for (int k = 0; k < 5; k++) ctx->stats.small[k] += t[k + 1] - t[k];
     ctx->stats.small_calls++;
+}
+
+// The end of an unpipelined verify of shard [b, b + n) on stream s: the verdicts (bitmap | status in d.bitmap, laid
+// out as vo) come back by one DMA through d.pin_out, the stream is waited for (the caller's drain guard is
+// disarmed once nothing is queued any more) and they are copied into the caller's arrays; t[3..5] and the account.
+template <class Drain>
+static int small_finish(cv_ctx *ctx, Device &d, hipStream_t s, Drain &drain, const VerdictOut &vo, size_t b, size_t n,
+                        const VerifyIn &in, double *t) {
+    CV_TRY(hipMemcpyAsync(d.pin_out.p, d.bitmap.p, in.status ? vo.o_st + n : vo.words * 8, hipMemcpyDeviceToHost, s));
+    t[3] = now_s();
+    CV_TRY(hipStreamSynchronize(s));
+    drain.armed = false;
+    t[4] = now_s();
+    std::memcpy(in.bitmap + b / 64, d.pin_out.p, vo.words * 8);
+    if (in.status) std::memcpy(in.status + b, d.pin_out.as<uint8_t>() + vo.o_st, n);
+    t[5] = now_s();
+    small_account(ctx, t);
+    return CV_OK;
 }
 
 // Zero-copy form of the small path for tri-chain batches (the notary batches).  The records are packed into
@@ -562,16 +618,14 @@ static int verify_shard_small_zc(cv_ctx *ctx, Device &d, const Opts &o, const St
     std::memset(nib + waves, 0, nnib - waves);   // bytes of waves past the batch: no wave stores them
     t[2] = now_s();
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });   // error paths: no kernel outlives the call
-    CV_TRY(ws_begin(d, sl, s));
-    const hipError_t e = cvk_verify_tri_zc(
-        &o.plan, (uint32_t)n, dv + st.o_pk, dv + st.o_sig, dv + st.o_ar - st.lo,
-        reinterpret_cast<const uint64_t *>(dv + st.o_off), reinterpret_cast<const uint32_t *>(dv + st.o_len),
-        d.zc_out.dev_as<uint8_t>(), in.status ? d.zc_out.dev_as<uint8_t>() + al16(nnib) : nullptr,
-        sl.ws_tab.as<uint32_t>(), sl.ws_ok.as<uint8_t>(), sl.ws_dig.as<uint32_t>(), sl.ws_cap, s,
-        gather ? d.zc_in.dev : nullptr, gather ? sl.packed.p : nullptr, gather ? al16(st.total) : 0);
-    const hipError_t e2 = ws_end(sl, s);
-    CV_TRY(e);
-    CV_TRY(e2);
+    CV_TRY(ws_run(d, sl, s, [&] {
+        return cvk_verify_tri_zc(
+            &o.plan, (uint32_t)n, dv + st.o_pk, dv + st.o_sig, dv + st.o_ar - st.lo,
+            reinterpret_cast<const uint64_t *>(dv + st.o_off), reinterpret_cast<const uint32_t *>(dv + st.o_len),
+            d.zc_out.dev_as<uint8_t>(), in.status ? d.zc_out.dev_as<uint8_t>() + al16(nnib) : nullptr,
+            sl.ws_tab.as<uint32_t>(), sl.ws_ok.as<uint8_t>(), sl.ws_dig.as<uint32_t>(), sl.ws_cap, s,
+            gather ? d.zc_in.dev : nullptr, gather ? sl.packed.p : nullptr, gather ? al16(st.total) : 0);
+    }));
     t[3] = now_s();
     CV_TRY(hipStreamSynchronize(s));
     drain.armed = false;
@@ -599,8 +653,7 @@ static int verify_shard_small_zc(cv_ctx *ctx, Device &d, const Opts &o, const St
 static int verify_shard_mid(cv_ctx *ctx, Device &d, const Opts &o, size_t b, size_t e, const VerifyIn &in,
                             WorkerPool *pool, double t_plan) {
     const size_t n = e - b;
-    const size_t words = (n + 63) / 64;
-    const size_t o_bm = 0, o_st = al16(words * 8), total_out = o_st + al16(n);
+    const VerdictOut vo(n);
     const size_t h_sig = al16(n * 32), h_total = h_sig + al16(n * 64);
     // pageable inputs go up in about 1 MB pieces of keys + signatures (at most CV_OPT_MID_PIECES)
     const size_t pieces = pool ? std::max<size_t>(1, std::min<size_t>(o.mid_pieces, h_total >> 20)) : 1;
@@ -616,8 +669,8 @@ static int verify_shard_mid(cv_ctx *ctx, Device &d, const Opts &o, size_t b, siz
     po.ready = sl.split.start;
     po.done = sl.split.done2;
     CV_TRY(sl.head.ensure(h_total));
-    CV_TRY(d.pin_out.ensure(total_out));
-    CV_TRY(d.bitmap.ensure(total_out));
+    CV_TRY(d.pin_out.ensure(vo.total_out));
+    CV_TRY(d.bitmap.ensure(vo.total_out));
     uint8_t *dh = sl.head.as<uint8_t>();
     hipStream_t aux = po.aux;
     auto drain = on_exit([s, aux] {   // error paths: no DMA or helper-stream kernel outlives the call
@@ -679,17 +732,8 @@ static int verify_shard_mid(cv_ctx *ctx, Device &d, const Opts &o, size_t b, siz
     uint8_t *dout = d.bitmap.as<uint8_t>();
     CV_TRY(launch_verify(d, o.plan, sl, (uint32_t)n, dh, dh + h_sig, dv + st.o_ar - st.lo,
                          reinterpret_cast<const uint64_t *>(dv + st.o_off), reinterpret_cast<const uint32_t *>(dv + st.o_len),
-                         reinterpret_cast<uint64_t *>(dout + o_bm), in.status ? dout + o_st : nullptr, s, nullptr, true, &po));
-    CV_TRY(hipMemcpyAsync(d.pin_out.p, dout, in.status ? o_st + n : words * 8, hipMemcpyDeviceToHost, s));
-    t[3] = now_s();
-    CV_TRY(hipStreamSynchronize(s));
-    drain.armed = false;
-    t[4] = now_s();
-    std::memcpy(in.bitmap + b / 64, d.pin_out.as<uint8_t>() + o_bm, words * 8);
-    if (in.status) std::memcpy(in.status + b, d.pin_out.as<uint8_t>() + o_st, n);
-    t[5] = now_s();
-    small_account(ctx, t);
-    return CV_OK;
+                         reinterpret_cast<uint64_t *>(dout), in.status ? dout + vo.o_st : nullptr, s, nullptr, true, &po));
+    return small_finish(ctx, d, s, drain, vo, b, n, in, t);
 }
 
 static int verify_shard_small(cv_ctx *ctx, Device &d, const Opts &o, size_t b, size_t e, const VerifyIn &in,
@@ -708,8 +752,7 @@ static int verify_shard_small(cv_ctx *ctx, Device &d, const Opts &o, size_t b, s
     if (o.small_zc && cvk_tri_zc_ok(&o.plan, (uint32_t)n, (uint32_t)n))
         return verify_shard_small_zc(ctx, d, o, st, b, in, pool, t_plan,
                                      o.small_zc == 2 || (o.small_zc == 3 && n >= 2048));
-    const size_t words = (n + 63) / 64;
-    const size_t o_bm = 0, o_st = al16(words * 8), total_out = o_st + al16(n);
+    const VerdictOut vo(n);
     double t[6];                 // host phases (cv_diag_stats CV_STATS_SMALL, as the zero-copy form)
     t[0] = t_plan;
     Slot &sl = d.slot[0];
@@ -717,9 +760,9 @@ static int verify_shard_small(cv_ctx *ctx, Device &d, const Opts &o, size_t b, s
     CV_TRY(slot_stream(d, 0, &s));
     CV_TRY(slot_events(sl));
     CV_TRY(sl.pin_in.ensure(st.total));
-    CV_TRY(d.pin_out.ensure(total_out));
+    CV_TRY(d.pin_out.ensure(vo.total_out));
     CV_TRY(sl.packed.ensure(st.total));
-    CV_TRY(d.bitmap.ensure(total_out));
+    CV_TRY(d.bitmap.ensure(vo.total_out));
     uint8_t *h = sl.pin_in.as<uint8_t>();
     uint8_t *dv = sl.packed.as<uint8_t>();
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });   // error paths: no DMA outlives the call
@@ -747,20 +790,58 @@ static int verify_shard_small(cv_ctx *ctx, Device &d, const Opts &o, size_t b, s
     uint8_t *dout = d.bitmap.as<uint8_t>();
     CV_TRY(launch_verify(d, o.plan, sl, (uint32_t)n, dv + st.o_pk, dv + st.o_sig, dv + st.o_ar - st.lo,
                          reinterpret_cast<const uint64_t *>(dv + st.o_off), reinterpret_cast<const uint32_t *>(dv + st.o_len),
-                         reinterpret_cast<uint64_t *>(dout + o_bm), in.status ? dout + o_st : nullptr, s, nullptr, true));
-    CV_TRY(hipMemcpyAsync(d.pin_out.p, dout, in.status ? o_st + n : words * 8, hipMemcpyDeviceToHost, s));
-    t[3] = now_s();
-    CV_TRY(hipStreamSynchronize(s));
-    drain.armed = false;
-    t[4] = now_s();
-    std::memcpy(in.bitmap + b / 64, d.pin_out.as<uint8_t>() + o_bm, words * 8);
-    if (in.status) std::memcpy(in.status + b, d.pin_out.as<uint8_t>() + o_st, n);
-    t[5] = now_s();
-    small_account(ctx, t);
-    return CV_OK;
+                         reinterpret_cast<uint64_t *>(dout), in.status ? dout + vo.o_st : nullptr, s, nullptr, true));
+    return small_finish(ctx, d, s, drain, vo, b, n, in, t);
 }
 
 // ---------------------------------------------------------------- the host pipeline
+// A finished synchronous call's timing events (CV_OPT_TIMELINE, PipeOut::tl) reduced to po.tl_sum; copy_ms: the
+// result copies' host-side time, from the join on.
+static void timeline_reduce(PipeOut &po, double copy_ms) {
+    auto at = [&](size_t k) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, po.tl[0], po.tl[k]);
+        return (double)ms;
+    };
+    const int J = po.tl_n;
+    // the union length of a set of [start, end) intervals
+    auto union_len = [](std::vector<std::pair<double, double>> iv) {
+        if (iv.empty()) return 0.0;
+        std::sort(iv.begin(), iv.end());
+        double busy = 0, cur0 = iv[0].first, cur1 = iv[0].second;
+        for (size_t j = 1; j < iv.size(); j++) {
+            if (iv[j].first > cur1) {
+                busy += cur1 - cur0;
+                cur0 = iv[j].first;
+                cur1 = iv[j].second;
+            } else {
+                cur1 = std::max(cur1, iv[j].second);
+            }
+        }
+        return busy + cur1 - cur0;
+    };
+    std::vector<std::pair<double, double>> all, mk, vf;
+    double ramp = 1e30, span = 0, dma_end = 0, mdma_end = 0;
+    for (int j = 0; j < J; j++) {
+        const std::pair<double, double> w{at(2 + 3 * (size_t)j), at(3 + 3 * (size_t)j)};
+        const double de = at(1 + 3 * (size_t)j);
+        const bool merkle = (size_t)j < po.tl_merkle.size() && po.tl_merkle[j];
+        all.push_back(w);
+        (merkle ? mk : vf).push_back(w);
+        ramp = std::min(ramp, w.first);
+        span = std::max(span, w.second);
+        dma_end = std::max(dma_end, de);
+        if (merkle) mdma_end = std::max(mdma_end, de);
+    }
+    const double busy = union_len(all);
+    const double v[kTlVals] = {ramp, dma_end, span, busy, span - ramp - busy, span - dma_end, copy_ms,
+                               (double)po.tl_first, union_len(mk), union_len(vf), mdma_end, (double)J,
+                               po.tl_pre_ms, 0.0};
+    for (int k = 0; k < kTlVals; k++) po.tl_sum[k] = v[k];
+    po.tl_ready = true;
+    po.tl_n = 0;
+}
+
 // Copies a finished pipelined call's results into the caller's arrays (waits for them first).  Results of
 // 1 MB and more are copied by the DMA straight into the caller's memory; smaller ones come back through
 // the output's pinned buffer.  The caller holds po.mu.
@@ -796,51 +877,7 @@ static int pipe_copy_back(Device &d, PipeOut &po) {
     if (!po.copied) CV_TRY(hipEventCreateWithFlags(&po.copied, hipEventDisableTiming));
     CV_TRY(hipEventRecord(po.copied, d.outs));
     CV_TRY(hipEventSynchronize(po.copied));
-    if (timeline) {
-        const double copy_ms = (now_s() - t_copy) * 1e3;
-        auto at = [&](size_t k) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, po.tl[0], po.tl[k]);
-            return (double)ms;
-        };
-        const int J = po.tl_n;
-        // the union length of a set of [start, end) intervals
-        auto union_len = [](std::vector<std::pair<double, double>> iv) {
-            if (iv.empty()) return 0.0;
-            std::sort(iv.begin(), iv.end());
-            double busy = 0, cur0 = iv[0].first, cur1 = iv[0].second;
-            for (size_t j = 1; j < iv.size(); j++) {
-                if (iv[j].first > cur1) {
-                    busy += cur1 - cur0;
-                    cur0 = iv[j].first;
-                    cur1 = iv[j].second;
-                } else {
-                    cur1 = std::max(cur1, iv[j].second);
-                }
-            }
-            return busy + cur1 - cur0;
-        };
-        std::vector<std::pair<double, double>> all, mk, vf;
-        double ramp = 1e30, span = 0, dma_end = 0, mdma_end = 0;
-        for (int j = 0; j < J; j++) {
-            const std::pair<double, double> w{at(2 + 3 * (size_t)j), at(3 + 3 * (size_t)j)};
-            const double de = at(1 + 3 * (size_t)j);
-            const bool merkle = (size_t)j < po.tl_merkle.size() && po.tl_merkle[j];
-            all.push_back(w);
-            (merkle ? mk : vf).push_back(w);
-            ramp = std::min(ramp, w.first);
-            span = std::max(span, w.second);
-            dma_end = std::max(dma_end, de);
-            if (merkle) mdma_end = std::max(mdma_end, de);
-        }
-        const double busy = union_len(all);
-        const double v[kTlVals] = {ramp, dma_end, span, busy, span - ramp - busy, span - dma_end, copy_ms,
-                                   (double)po.tl_first, union_len(mk), union_len(vf), mdma_end, (double)J,
-                                   po.tl_pre_ms, 0.0};
-        for (int k = 0; k < kTlVals; k++) po.tl_sum[k] = v[k];
-        po.tl_ready = true;
-        po.tl_n = 0;
-    }
+    if (timeline) timeline_reduce(po, (now_s() - t_copy) * 1e3);
     for (int k = 0; k < po.nseg; k++) {
         const PipeOut::Seg &sg = po.seg[k];
         if (sg.len && sg.len < kDirect) std::memcpy(sg.dst, po.hout.as<uint8_t>() + sg.off, sg.len);
@@ -888,16 +925,61 @@ struct MerkleIn {
 };
 
 // The common frame of a pipelined call on one device: the two compute streams, the ring's events and the
-// output's completion events; and the error-path drain.
+// output's completion events; the staging step of a sub-chunk; and the error-path drain.  An enqueue function
+// opens it with begin() and closes it with end(); a return in between drains (the destructor).
 struct PipeFrame {
     Device &d;
     PipeOut &po;
-    int ns = 2;                       // compute slots this call uses (CV_OPT_PIPE_SLOTS for verify calls; set before init)
+    int ns = 2;                       // compute slots this call uses (CV_OPT_PIPE_SLOTS for verify calls; set before begin)
     hipStream_t ss[kPipeSlots] = {};
     bool used[kPipeSlots + 1] = {};   // + the copy stream (Merkle kernels), always at index kPipeSlots
     double t[5] = {};   // plan, pack, wait, enqueue (seconds)
     uint64_t chunks = 0, direct = 0;
     bool tl = false;    // CV_OPT_TIMELINE: record po.tl's events (synchronous verify calls)
+    bool armed = false; // between begin() and end(): leaving the enqueue function drains
+    WorkerPool *pool = nullptr;   // the device's host packing threads
+    ~PipeFrame() {
+        if (armed) drain();
+    }
+    // Opens the frame: streams and events, the output's device block of total_out bytes, the drain guard, the
+    // packing threads; timeline: this call records po.tl's events (its summary fields start afresh either way).
+    int begin(size_t total_out, int threads, bool timeline) {
+        CV_TRY(hipSetDevice(d.ordinal));
+        const int rc = init();
+        if (rc != CV_OK) return rc;
+        CV_TRY(po.dout.ensure(total_out));
+        armed = true;
+        pool = &d.workers(threads);
+        tl = timeline;
+        po.tl_ready = false;
+        po.tl_merkle.clear();
+        po.tl_pre_ms = 0;
+        po.tl_first = 0;
+        return CV_OK;
+    }
+    // Closes the frame: the completion marks, the drain guard off, where the results go (segments with a null
+    // destination are left out) and the call's counts — pipe: its sub-chunks count as pipe sub-chunks (a Merkle-only
+    // call's count as Merkle sub-chunks only), keyed: a keyed call, merkle: its Merkle sub-chunks.
+    int end(cv_ctx *ctx, std::initializer_list<PipeOut::Seg> segs, bool pipe, bool keyed, uint64_t merkle) {
+        const int rc = complete();
+        if (rc != CV_OK) return rc;
+        armed = false;
+        po.nseg = 0;
+        for (const PipeOut::Seg &sg : segs)
+            if (sg.dst) po.seg[po.nseg++] = sg;
+        std::lock_guard<std::mutex> g(ctx->st_mu);
+        Stats &S = ctx->stats;
+        for (int k = 0; k < 4; k++) S.pipe[k] += t[k];
+        S.pipe_calls++;
+        if (pipe) S.pipe_chunks += chunks;
+        S.pipe_direct += direct;
+        if (keyed) {
+            S.keyed_calls++;
+            S.keyed_chunks += chunks;
+        }
+        S.merkle_chunks += merkle;
+        return CV_OK;
+    }
     hipError_t tl_record(size_t k, hipStream_t s) {
         hipEvent_t e = po.tl_ev(k);
         return e ? hipEventRecord(e, s) : hipErrorOutOfMemory;
@@ -983,35 +1065,47 @@ struct PipeFrame {
         d.stage_busy[k] = true;
         return CV_OK;
     }
-    // Stages Merkle sub-chunk st into the next ring block (hint: as block()): DMAed straight from the caller's
-    // arrays when they are pinned, else packed into the next staging block and moved by one copy.  *ta: in, when
-    // the sub-chunk's planning began (the plan time runs from it); out, when its enqueue phase began (the caller
-    // adds t[3] from it once the sub-chunk's kernels are enqueued).
-    int stage_merkle(const MStage &st, const MerkleIn &in, WorkerPool *pool, size_t hint, double *ta, int *q,
-                     uint8_t **dv) {
-        const bool dma = mstage_direct(st, in.txb, in.arena, in.off, in.len);
+    // One staging step: `bytes` of a sub-chunk into the next ring block (hint: as block()).  direct: the caller's
+    // arrays are pinned and dma(dv) issues its copies straight from them on the copy stream; else pack(h, dv, &sent)
+    // fills the next pinned staging block h — it may already have sent a prefix h[0, sent) itself, mid-way — and one
+    // copy moves the rest.  *ta: in, when the sub-chunk's planning began (the plan time runs from it); out, when
+    // its enqueue phase began (the caller adds t[3] from it once the sub-chunk's kernels are enqueued).
+    template <class Dma, class Pack>
+    int stage(size_t bytes, size_t hint, bool direct, Dma dma, Pack pack, int *q, uint8_t **dv, double *ta) {
         double tb = now_s();
         t[0] += tb - *ta;
-        int rc = block(q, st.total, dv, hint);
+        int rc = block(q, bytes, dv, hint);
         if (rc != CV_OK) return rc;
-        if (dma) {
+        if (direct) {
             *ta = now_s();
             t[2] += *ta - tb;
-            CV_TRY(mstage_dma_direct(st, *dv, in.txb, in.arena, in.off, in.len, d.copy));
-            direct++;
+            if ((rc = dma(*dv)) != CV_OK) return rc;
+            this->direct++;
             return CV_OK;
         }
         uint8_t *h;
         int sk;
-        if ((rc = staging(&sk, st.total, &h)) != CV_OK) return rc;
+        if ((rc = staging(&sk, bytes, &h)) != CV_OK) return rc;
         *ta = now_s();
         t[2] += *ta - tb;
-        mstage_pack(st, h, in.txb, in.arena, in.off, in.len, pool);
+        size_t sent = 0;
+        if ((rc = pack(h, *dv, &sent)) != CV_OK) return rc;
         tb = now_s();
         t[1] += tb - *ta;
         *ta = tb;
-        CV_TRY(hipMemcpyAsync(*dv, h, st.total, hipMemcpyHostToDevice, d.copy));
+        CV_TRY(hipMemcpyAsync(*dv + sent, h + sent, bytes - sent, hipMemcpyHostToDevice, d.copy));
         return staged(sk);
+    }
+    // stage() for Merkle sub-chunk st
+    int stage_merkle(const MStage &st, const MerkleIn &in, size_t hint, double *ta, int *q, uint8_t **dv) {
+        return stage(
+            st.total, hint, mstage_direct(st, in.txb, in.arena, in.off, in.len),
+            [&](uint8_t *v) { return hip_rc(mstage_dma_direct(st, v, in.txb, in.arena, in.off, in.len, d.copy)); },
+            [&](uint8_t *h, uint8_t *, size_t *) {
+                mstage_pack(st, h, in.txb, in.arena, in.off, in.len, pool);
+                return CV_OK;
+            },
+            q, dv, ta);
     }
     // after sub-chunk j's copies into block q: compute stream j % 2 (or `on`) waits for them
     int copied(int q, int j, bool start_recorded = false, hipStream_t on = nullptr) {
@@ -1051,14 +1145,6 @@ struct PipeFrame {
         po.gen++;
         return CV_OK;
     }
-    void account(cv_ctx *ctx) {
-        std::lock_guard<std::mutex> g(ctx->st_mu);
-        Stats &S = ctx->stats;
-        for (int k = 0; k < 4; k++) S.pipe[k] += t[k];
-        S.pipe_calls++;
-        S.pipe_chunks += chunks;
-        S.pipe_direct += direct;
-    }
 };
 
 // Enqueues the pipelined verify of shard [b, e) on device d into output po (held, not pending); returns
@@ -1086,17 +1172,13 @@ struct PipeFrame {
 static int pipe_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_t b, size_t e, const VerifyIn &in,
                         int threads, bool async) {
     const size_t n = e - b;
-    const size_t words = (n + 63) / 64;
-    const size_t o_st = al16(words * 8), total_out = o_st + al16(n);
+    const VerdictOut vo(n);
     PipeFrame f{d, po};
     f.ns = (int)o.pipe_slots;
-    CV_TRY(hipSetDevice(d.ordinal));
-    int rc = f.init();
+    int rc = f.begin(vo.total_out, threads, o.timeline && !async);
     if (rc != CV_OK) return rc;
-    CV_TRY(po.dout.ensure(total_out));
     uint8_t *dout = po.dout.as<uint8_t>();
-    auto drain = on_exit([&f] { f.drain(); });
-    WorkerPool *pool = &d.workers(threads);
+    WorkerPool *pool = f.pool;
     const bool keyed = in.keys != nullptr;
     // ---- keyed: the shard's distinct keys, resident in the pool, uploaded with their slots
     const uint8_t *keys = in.keys;
@@ -1143,10 +1225,6 @@ static int pipe_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size
     const std::vector<size_t> cut = async ? pipe_cuts(b, e, ach, ach, false) : pipe_cuts(b, e, o.pipe_first, sch, true);
     size_t max_m = 1;
     for (size_t j = 0; j + 1 < cut.size(); j++) max_m = std::max(max_m, cut[j + 1] - cut[j]);
-    f.tl = o.timeline && !async;
-    po.tl_ready = false;
-    po.tl_merkle.clear();
-    po.tl_pre_ms = 0;
     po.tl_first = cut.size() > 1 ? cut[1] - cut[0] : 0;
     for (size_t j = 0; j + 1 < cut.size(); j++) {
         const size_t c0 = cut[j], c1 = cut[j + 1], m = c1 - c0;
@@ -1156,12 +1234,6 @@ static int pipe_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size
         const Stage st = stage_plan(c0, c1, in.off, in.len, pool, keyed);
         if (!stage_in_bounds(st, in.arena_bytes)) return CV_E_ARGS;   // before this sub-chunk's copy (drain: the ones before it)
         const bool direct = stage_direct(st, c0, in.pk, kidx, in.sig, in.arena, in.off, in.len);
-        double t1 = now_s();
-        f.t[0] += t1 - t0;
-        int q;
-        uint8_t *dv;
-        if ((rc = f.block(&q, st.total, &dv, (size_t)((double)st.total / (double)m * (double)max_m))) != CV_OK) return rc;
-        if (f.tl && j == 0) CV_TRY(f.tl_record(0, d.copy));
         // Synchronous calls: the first sub-chunk's keys and signatures (all the point decodes read: 96 of its ~400 B
         // per C2 record) are DMAed first and its point blocks start on the slot's helper stream as soon as they
         // land, beside the rest of the DMA and the scalars (CvkPrepOverlap, as the mid-size path): the ramp before
@@ -1174,41 +1246,37 @@ static int pipe_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size
             pov.ready = sl.split.start;
             pov.done = sl.split.done2;
         }
-        if (direct) {
-            t0 = now_s();
-            f.t[2] += t0 - t1;
-            if (overlap0) {
-                CV_TRY(hipMemcpyAsync(dv + st.o_pk, in.pk + c0 * 32, m * 32, hipMemcpyHostToDevice, d.copy));
-                CV_TRY(hipMemcpyAsync(dv + st.o_sig, in.sig + c0 * 64, m * 64, hipMemcpyHostToDevice, d.copy));
+        // (timeline: the call's first input DMA starts here, behind the copy stream's wait for its ring block)
+        auto first_dma = [&] { return f.tl && j == 0 ? f.tl_record(0, d.copy) : hipSuccess; };
+        int q;
+        uint8_t *dv;
+        rc = f.stage(
+            st.total, (size_t)((double)st.total / (double)m * (double)max_m), direct,
+            [&](uint8_t *v) {
+                CV_TRY(first_dma());
+                if (!overlap0) return hip_rc(stage_dma_direct(st, v, c0, in.pk, kidx, in.sig, in.arena, in.off, in.len, d.copy));
+                CV_TRY(hipMemcpyAsync(v + st.o_pk, in.pk + c0 * 32, m * 32, hipMemcpyHostToDevice, d.copy));
+                CV_TRY(hipMemcpyAsync(v + st.o_sig, in.sig + c0 * 64, m * 64, hipMemcpyHostToDevice, d.copy));
                 CV_TRY(hipEventRecord(pov.ready, d.copy));
-                CV_TRY(hipMemcpyAsync(dv + st.o_off, in.off + c0, m * 8, hipMemcpyHostToDevice, d.copy));
-                CV_TRY(hipMemcpyAsync(dv + st.o_len, in.len + c0, m * 4, hipMemcpyHostToDevice, d.copy));
+                CV_TRY(hipMemcpyAsync(v + st.o_off, in.off + c0, m * 8, hipMemcpyHostToDevice, d.copy));
+                CV_TRY(hipMemcpyAsync(v + st.o_len, in.len + c0, m * 4, hipMemcpyHostToDevice, d.copy));
                 if (st.hi > st.lo)
-                    CV_TRY(hipMemcpyAsync(dv + st.o_ar, in.arena + st.lo, st.hi - st.lo, hipMemcpyHostToDevice, d.copy));
-            } else {
-                CV_TRY(stage_dma_direct(st, dv, c0, in.pk, kidx, in.sig, in.arena, in.off, in.len, d.copy));
-            }
-            f.direct++;
-        } else {
-            uint8_t *h;
-            int sk;
-            if ((rc = f.staging(&sk, st.total, &h)) != CV_OK) return rc;
-            t0 = now_s();
-            f.t[2] += t0 - t1;
-            hipError_t e1 = hipSuccess;
-            stage_pack(st, h, c0, in.pk, kidx, in.sig, in.arena, in.off, in.len, pool, [&] {
-                if (!overlap0) return;
-                e1 = hipMemcpyAsync(dv, h, st.o_off, hipMemcpyHostToDevice, d.copy);
-                if (e1 == hipSuccess) e1 = hipEventRecord(pov.ready, d.copy);
-            });
-            CV_TRY(e1);
-            t1 = now_s();
-            f.t[1] += t1 - t0;
-            t0 = t1;
-            const size_t from = overlap0 ? st.o_off : 0;
-            CV_TRY(hipMemcpyAsync(dv + from, h + from, st.total - from, hipMemcpyHostToDevice, d.copy));
-            if ((rc = f.staged(sk)) != CV_OK) return rc;
-        }
+                    CV_TRY(hipMemcpyAsync(v + st.o_ar, in.arena + st.lo, st.hi - st.lo, hipMemcpyHostToDevice, d.copy));
+                return CV_OK;
+            },
+            [&](uint8_t *h, uint8_t *v, size_t *sent) {
+                CV_TRY(first_dma());
+                hipError_t e1 = hipSuccess;
+                stage_pack(st, h, c0, in.pk, kidx, in.sig, in.arena, in.off, in.len, pool, [&] {
+                    if (!overlap0) return;
+                    e1 = hipMemcpyAsync(v, h, st.o_off, hipMemcpyHostToDevice, d.copy);
+                    if (e1 == hipSuccess) e1 = hipEventRecord(pov.ready, d.copy);
+                    *sent = st.o_off;
+                });
+                return hip_rc(e1);
+            },
+            &q, &dv, &t0);
+        if (rc != CV_OK) return rc;
         if (f.tl && j == 0 && in.t_entry > 0) po.tl_pre_ms = (now_s() - in.t_entry) * 1e3;
         if (f.tl && overlap0) {   // the timeline's first kernel start: the point blocks on the helper stream
             CV_TRY(hipStreamWaitEvent(pov.aux, pov.ready, 0));
@@ -1219,18 +1287,15 @@ static int pipe_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size
         const uint64_t *doff = reinterpret_cast<const uint64_t *>(dv + st.o_off);
         const uint32_t *dlen = reinterpret_cast<const uint32_t *>(dv + st.o_len);
         uint64_t *dbm = reinterpret_cast<uint64_t *>(dout) + w0;
-        uint8_t *dst = in.status ? dout + o_st + (c0 - b) : nullptr;
+        uint8_t *dst = in.status ? dout + vo.o_st + (c0 - b) : nullptr;
         if (keyed) {
             CV_TRY(ensure_verify_ws(sl, m));
-            CV_TRY(ws_begin(d, sl, s));
-            const hipError_t ek = cvk_verify_keyed(&o.plan, (uint32_t)m, kdev_keys, reinterpret_cast<const uint32_t *>(dv + st.o_kidx),
-                                                   kdev_slot, d.kc.ktab.as<uint32_t>(), d.kc.kok.as<uint8_t>(),
-                                                   dv + st.o_sig, dv + st.o_ar - st.lo, doff, dlen, dbm, dst,
-                                                   sl.ws_hs.as<uint32_t>(), sl.ws_R.as<uint32_t>(), sl.ws_ok.as<uint8_t>(),
-                                                   sl.ws_cap, s, nullptr);
-            const hipError_t e2 = ws_end(sl, s);
-            CV_TRY(ek);
-            CV_TRY(e2);
+            CV_TRY(ws_run(d, sl, s, [&] {
+                return cvk_verify_keyed(&o.plan, (uint32_t)m, kdev_keys, reinterpret_cast<const uint32_t *>(dv + st.o_kidx),
+                                        kdev_slot, d.kc.ktab.as<uint32_t>(), d.kc.kok.as<uint8_t>(), dv + st.o_sig,
+                                        dv + st.o_ar - st.lo, doff, dlen, dbm, dst, sl.ws_hs.as<uint32_t>(),
+                                        sl.ws_R.as<uint32_t>(), sl.ws_ok.as<uint8_t>(), sl.ws_cap, s, nullptr);
+            }));
         } else {
             CV_TRY(launch_verify(d, o.plan, sl, (uint32_t)m, dv + st.o_pk, dv + st.o_sig, dv + st.o_ar - st.lo, doff, dlen,
                                  dbm, dst, s, nullptr, false, overlap0 ? &pov : nullptr));
@@ -1238,19 +1303,11 @@ static int pipe_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size
         if ((rc = f.launched(q, (int)j)) != CV_OK) return rc;
         f.t[3] += now_s() - t0;
     }
-    if (keyed) {
+    if (keyed)
         for (int k = 0; k < f.ns; k++)
             if (f.used[k]) CV_TRY(pool_end(d.kc, f.ss[k]));   // (the pool's last user: either stream)
-        std::lock_guard<std::mutex> g(ctx->st_mu);
-        ctx->stats.keyed_chunks += f.chunks;
-    }
-    if ((rc = f.complete()) != CV_OK) return rc;
-    drain.armed = false;
-    po.nseg = 0;
-    po.seg[po.nseg++] = {in.bitmap + b / 64, 0, words * 8};
-    if (in.status) po.seg[po.nseg++] = {in.status + b, o_st, n};
-    f.account(ctx);
-    return CV_OK;
+    return f.end(ctx, {{in.bitmap + b / 64, 0, vo.words * 8}, {in.status ? in.status + b : nullptr, vo.o_st, n}}, true,
+                 keyed, 0);
 }
 
 // The Merkle kernels of a staged sub-chunk on stream s: the stage's parts in its device block dv, the leaf digests
@@ -1281,13 +1338,9 @@ static int merkle_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, si
     const size_t nt = t1 - t0;
     const size_t o_st = al16(nt * 32), total_out = o_st + al16(nt);
     PipeFrame f{d, po};
-    CV_TRY(hipSetDevice(d.ordinal));
-    int rc = f.init();
+    int rc = f.begin(total_out, threads, false);
     if (rc != CV_OK) return rc;
-    CV_TRY(po.dout.ensure(total_out));
     uint8_t *dout = po.dout.as<uint8_t>();
-    auto drain = on_exit([&f] { f.drain(); });
-    WorkerPool *pool = &d.workers(threads);
     // sub-chunk cuts: whole transactions, about merkle_chunk leaves each (at least one transaction), and at most
     // ~12 per shard, so one call's copies fit the ring ahead of its kernels
     const size_t nl_all = in.txb[t1] - in.txb[t0];
@@ -1318,40 +1371,28 @@ static int merkle_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, si
             const MStage &st = p.st;
             CV_TRY(launch_merkle(st, p.dv, d.digest.as<uint32_t>(), dout + (st.t0 - t0) * 32, dout + o_st + (st.t0 - t0),
                                  d.copy));
-            CV_TRY(hipEventRecord(d.in_free[p.q], d.copy));
-            d.in_used[p.q] = true;
-            f.chunks++;
+            const int r = f.launched(p.q, (int)f.chunks, d.copy);
+            if (r != CV_OK) return r;
         }
         pend.clear();
-        f.used[kPipeSlots] = true;
         f.t[3] += now_s() - ta;
         return CV_OK;
     };
     for (size_t j = 0; j + 1 < cut.size(); j++) {
         const size_t c0 = cut[j], c1 = cut[j + 1];
         double ta = now_s();
-        const MStage st = mstage_plan(c0, c1, in.txb, in.off, in.len, pool);
+        const MStage st = mstage_plan(c0, c1, in.txb, in.off, in.len, f.pool);
         if (!mstage_in_bounds(st, in.arena_bytes)) return CV_E_ARGS;   // past the arena, or a leaf's off + len wraps
         int q;
         uint8_t *dv;
-        if ((rc = f.stage_merkle(st, in, pool, 0, &ta, &q, &dv)) != CV_OK) return rc;
+        if ((rc = f.stage_merkle(st, in, 0, &ta, &q, &dv)) != CV_OK) return rc;
         f.t[3] += now_s() - ta;
         pend.push_back({st, q, dv});
         if (pend.size() + 2 >= (size_t)kRing && (rc = flush()) != CV_OK) return rc;
     }
     if ((rc = flush()) != CV_OK) return rc;
-    if ((rc = f.complete()) != CV_OK) return rc;
-    drain.armed = false;
-    po.nseg = 0;
-    po.seg[po.nseg++] = {in.ids + t0 * 32, 0, nt * 32};
-    if (in.status) po.seg[po.nseg++] = {in.status + t0, o_st, nt};
-    f.account(ctx);
-    {
-        std::lock_guard<std::mutex> g(ctx->st_mu);
-        ctx->stats.merkle_chunks += cut.size() - 1;
-        ctx->stats.pipe_chunks -= f.chunks;   // counted as Merkle sub-chunks only
-    }
-    return CV_OK;
+    return f.end(ctx, {{in.ids + t0 * 32, 0, nt * 32}, {in.status ? in.status + t0 : nullptr, o_st, nt}}, false, false,
+                 cut.size() - 1);
 }
 
 // One shard of a small synchronous Merkle call (a resolve chain's or a notary batch's transactions, staging below
@@ -1395,11 +1436,7 @@ static int merkle_shard_small(Device &d, const MStage &st, const MerkleIn &in, W
         CV_TRY(hipMemcpyAsync(dv, sl.pin_in.p, st.total, hipMemcpyHostToDevice, s));
     }
     uint8_t *dout = d.ids.as<uint8_t>();
-    CV_TRY(ws_begin(d, sl, s));
-    const hipError_t ek = launch_merkle(st, dv, sl.mdig.as<uint32_t>(), dout, dout + o_st, s);
-    const hipError_t e2 = ws_end(sl, s);
-    CV_TRY(ek);
-    CV_TRY(e2);
+    CV_TRY(ws_run(d, sl, s, [&] { return launch_merkle(st, dv, sl.mdig.as<uint32_t>(), dout, dout + o_st, s); }));
     CV_TRY(hipMemcpyAsync(d.pin_out.p, dout, in.status ? o_st + nt : nt * 32, hipMemcpyDeviceToHost, s));
     CV_TRY(hipStreamSynchronize(s));
     drain.armed = false;
@@ -1443,22 +1480,14 @@ static int txs_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_
     const size_t o_len = o_off + al16(ns * 8), o_tsb = o_len + al16(ns * 4), total_out = o_tsb + al16((nt + 1) * 4);
     PipeFrame f{d, po};
     f.ns = (int)o.pipe_slots;
-    CV_TRY(hipSetDevice(d.ordinal));
-    int rc = f.init();
+    int rc = f.begin(total_out, threads, o.timeline && !async);   // (timeline: groups tagged Merkle / verify in po.tl_merkle)
     if (rc != CV_OK) return rc;
-    CV_TRY(po.dout.ensure(total_out));
     uint8_t *dout = po.dout.as<uint8_t>();
+    WorkerPool *pool = f.pool;
     const uint32_t *dtsb = reinterpret_cast<const uint32_t *>(dout + o_tsb);
     uint64_t *doff = reinterpret_cast<uint64_t *>(dout + o_off);
     uint32_t *dlen = reinterpret_cast<uint32_t *>(dout + o_len);
     uint64_t *dbm = reinterpret_cast<uint64_t *>(dout + o_bm);
-    auto drain = on_exit([&f] { f.drain(); });
-    WorkerPool *pool = &d.workers(threads);
-    f.tl = o.timeline && !async;   // (timeline: groups tagged Merkle / verify in po.tl_merkle)
-    po.tl_ready = false;
-    po.tl_merkle.clear();
-    po.tl_pre_ms = 0;
-    po.tl_first = 0;
     if (f.tl) CV_TRY(f.tl_record(0, d.copy));
     // the shard's signature boundaries go first on the copy stream, so every group's copy event covers them
     {
@@ -1533,30 +1562,22 @@ static int txs_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_
             if (!last && m < vmin) break;
             double ta = now_s();
             const size_t o_sig = al16(m * 32), bytes = o_sig + al16(m * 64);
+            const uint8_t *pk = in.pk + p * 32, *sig = in.sig + p * 64;
             int q;
             uint8_t *dv;
-            int r = f.block(&q, bytes, &dv, al16(vch * 32) + al16(vch * 64));
+            int r = f.stage(
+                bytes, al16(vch * 32) + al16(vch * 64), host_pinned(pk, m * 32) && host_pinned(sig, m * 64),
+                [&](uint8_t *v) {
+                    CV_TRY(hipMemcpyAsync(v, pk, m * 32, hipMemcpyHostToDevice, d.copy));
+                    CV_TRY(hipMemcpyAsync(v + o_sig, sig, m * 64, hipMemcpyHostToDevice, d.copy));
+                    return CV_OK;
+                },
+                [&](uint8_t *h, uint8_t *, size_t *) {
+                    par_copy({{h, pk, m * 32}, {h + o_sig, sig, m * 64}}, pool);
+                    return CV_OK;
+                },
+                &q, &dv, &ta);
             if (r != CV_OK) return r;
-            double tb;
-            if (host_pinned(in.pk + p * 32, m * 32) && host_pinned(in.sig + p * 64, m * 64)) {
-                tb = now_s();
-                f.t[2] += tb - ta;
-                CV_TRY(hipMemcpyAsync(dv, in.pk + p * 32, m * 32, hipMemcpyHostToDevice, d.copy));
-                CV_TRY(hipMemcpyAsync(dv + o_sig, in.sig + p * 64, m * 64, hipMemcpyHostToDevice, d.copy));
-                f.direct++;
-            } else {
-                uint8_t *h;
-                int sk;
-                if ((r = f.staging(&sk, bytes, &h)) != CV_OK) return r;
-                tb = now_s();
-                f.t[2] += tb - ta;
-                par_copy({{h, in.pk + p * 32, m * 32}, {h + o_sig, in.sig + p * 64, m * 64}}, pool);
-                ta = now_s();
-                f.t[1] += ta - tb;
-                tb = ta;
-                CV_TRY(hipMemcpyAsync(dv, h, bytes, hipMemcpyHostToDevice, d.copy));
-                if ((r = f.staged(sk)) != CV_OK) return r;
-            }
             const int ks = mst ? vg++ % f.ns : g % f.ns;
             Slot &sl = d.slot[ks];
             hipStream_t s = f.ss[ks];
@@ -1572,7 +1593,7 @@ static int txs_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_
                                  in.sig_status ? dout + o_sst + c0 : nullptr, s, nullptr, false));
             if (f.tl) po.tl_merkle.push_back(0);
             if ((r = f.launched(q, g++, s)) != CV_OK) return r;
-            f.t[3] += now_s() - tb;
+            f.t[3] += now_s() - ta;
             p += m;
         }
         return CV_OK;
@@ -1582,11 +1603,7 @@ static int txs_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_
     // its ids start.  On a stream of its own it waits for nothing but its leaves, so the signature groups of
     // sub-chunk J follow it directly: the call's first signature group no longer waits for a second Merkle group's
     // copy (the loop's fill)
-#ifdef CV_TXS_LAG   // (A/B builds only)
-    const size_t lag = CV_TXS_LAG;
-#else
     const size_t lag = mst ? 0 : 1;
-#endif
     for (size_t J = 0; J < nm; J++) {
         double ta = now_s();
         const MStage st = mstage_plan(mcut[J], mcut[J + 1], mi.txb, mi.off, mi.len, pool);
@@ -1594,18 +1611,16 @@ static int txs_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_
         int q;
         uint8_t *dv;
         const size_t hint = (size_t)((double)st.total / (double)std::max<size_t>(1, st.l1 - st.l0) * (double)max_nl);
-        if ((rc = f.stage_merkle(st, mi, pool, hint, &ta, &q, &dv)) != CV_OK) return rc;
+        if ((rc = f.stage_merkle(st, mi, hint, &ta, &q, &dv)) != CV_OK) return rc;
         hipStream_t s = mst ? mst : f.ss[g % f.ns];
         if ((rc = f.copied(q, g, false, s)) != CV_OK) return rc;
-        {
-            Slot *sl = mst ? nullptr : &d.slot[g % f.ns];
-            if (sl) CV_TRY(ws_begin(d, *sl, s));
-            const hipError_t ek = launch_merkle(st, dv, sl ? sl->mdig.as<uint32_t>() : mdig->as<uint32_t>(),
-                                                dout + (st.t0 - t0) * 32, dout + o_mst + (st.t0 - t0), s);
-            const hipError_t e2 = sl ? ws_end(*sl, s) : hipSuccess;
-            CV_TRY(ek);
-            CV_TRY(e2);
-            if (sl) CV_TRY(hipEventRecord(d.mev[J], s));
+        uint8_t *dids = dout + (st.t0 - t0) * 32, *dmst = dout + o_mst + (st.t0 - t0);
+        if (mst) {
+            CV_TRY(launch_merkle(st, dv, mdig->as<uint32_t>(), dids, dmst, s));
+        } else {
+            Slot &sl = d.slot[g % f.ns];
+            CV_TRY(ws_run(d, sl, s, [&] { return launch_merkle(st, dv, sl.mdig.as<uint32_t>(), dids, dmst, s); }));
+            CV_TRY(hipEventRecord(d.mev[J], s));
         }
         if (f.tl) po.tl_merkle.push_back(1);
         if ((rc = f.launched(q, g++, s)) != CV_OK) return rc;
@@ -1630,19 +1645,12 @@ static int txs_enqueue(cv_ctx *ctx, Device &d, const Opts &o, PipeOut &po, size_
         CV_TRY(cvk_tx_verdicts((uint32_t)nt, (uint32_t)s0, dtsb, dout + o_mst, dbm, dout + o_ok, s));
         f.mark_used(s);
     }
-    if ((rc = f.complete()) != CV_OK) return rc;
-    drain.armed = false;
-    po.nseg = 0;
-    po.seg[po.nseg++] = {in.tx_ok + t0, o_ok, nt};
-    if (mi.ids) po.seg[po.nseg++] = {mi.ids + t0 * 32, 0, nt * 32};
-    if (mi.status) po.seg[po.nseg++] = {mi.status + t0, o_mst, nt};
-    if (in.sig_status && ns) po.seg[po.nseg++] = {in.sig_status + s0, o_sst, ns};
-    f.account(ctx);
-    {
-        std::lock_guard<std::mutex> g2(ctx->st_mu);
-        ctx->stats.merkle_chunks += nm;
-    }
-    return CV_OK;
+    return f.end(ctx,
+                 {{in.tx_ok + t0, o_ok, nt},
+                  {mi.ids ? mi.ids + t0 * 32 : nullptr, 0, nt * 32},
+                  {mi.status ? mi.status + t0 : nullptr, o_mst, nt},
+                  {in.sig_status && ns ? in.sig_status + s0 : nullptr, o_sst, ns}},
+                 true, false, nm);
 }
 
 // A finished synchronous call's GPU timeline (CV_OPT_TIMELINE) into the context's sums.  The caller holds st_mu.
@@ -1656,6 +1664,34 @@ static void timeline_account(cv_ctx *ctx, PipeOut &po) {
 
 // A pipelined call's part on one device, for its ticket: (device index, output index, gen).
 using Part = std::array<uint64_t, 3>;
+
+// The frame of one pipelined shard on device d: takes the device's next output (finishing that output's previous
+// call if still pending), runs enqueue(PipeOut &) on it, then either records the output in *part for the call's
+// ticket (async) or waits for it, results into the caller's arrays.  The wait for the output and the finish are
+// CV_STATS_PIPE's host times [2] and [4], whichever call the shard belongs to.
+template <class E>
+static int shard_pipelined(cv_ctx *ctx, Device &d, bool async, Part *part, E enqueue) {
+    int k = 0;
+    std::unique_lock<std::mutex> lk;
+    const double tw = now_s();
+    PipeOut &po = pipe_out(d, &k, lk);
+    const double t0 = now_s();
+    int rc = enqueue(po);
+    double finish = 0;
+    if (rc == CV_OK && async) {
+        *part = {(uint64_t)dev_index(ctx, d), (uint64_t)k, po.gen};
+        po.ticketed = true;
+    } else if (rc == CV_OK) {
+        const double t1 = now_s();
+        rc = pipe_finish(d, po);
+        finish = now_s() - t1;
+    }
+    std::lock_guard<std::mutex> g(ctx->st_mu);
+    ctx->stats.pipe[2] += t0 - tw;
+    ctx->stats.pipe[4] += finish;
+    if (!async) timeline_account(ctx, po);
+    return rc;
+}
 
 // One shard of a verify call on device d.  Synchronous calls: small plain shards take the one-DMA (or
 // zero-copy) path, the rest the pipeline and wait for it; asynchronous calls always take the pipeline and
@@ -1689,33 +1725,9 @@ static int verify_shard(cv_ctx *ctx, Device &d, const Opts &o, size_t b, size_t 
         }
         in.used = used.data();
     }
-    const bool keyed = in.keys != nullptr;
-    if (!async && !keyed && n <= o.pipe_min) return verify_shard_small(ctx, d, o, b, e, in, threads);
-    int k = 0;
-    std::unique_lock<std::mutex> lk;
-    const double tw = now_s();
-    PipeOut &po = pipe_out(d, &k, lk);   // (finishes that output's previous call if still pending)
-    {
-        std::lock_guard<std::mutex> g(ctx->st_mu);
-        ctx->stats.pipe[2] += now_s() - tw;
-    }
-    int rc = pipe_enqueue(ctx, d, o, po, b, e, in, threads, async);
-    if (rc != CV_OK) return rc;
-    if (keyed) {
-        std::lock_guard<std::mutex> g(ctx->st_mu);
-        ctx->stats.keyed_calls++;
-    }
-    if (async) {
-        *part = {(uint64_t)dev_index(ctx, d), (uint64_t)k, po.gen};
-        po.ticketed = true;
-        return CV_OK;
-    }
-    const double t0 = now_s();
-    rc = pipe_finish(d, po);
-    std::lock_guard<std::mutex> g(ctx->st_mu);
-    ctx->stats.pipe[4] += now_s() - t0;
-    timeline_account(ctx, po);
-    return rc;
+    if (!async && !in.keys && n <= o.pipe_min) return verify_shard_small(ctx, d, o, b, e, in, threads);
+    return shard_pipelined(ctx, d, async, part,
+                           [&](PipeOut &po) { return pipe_enqueue(ctx, d, o, po, b, e, in, threads, async); });
 }
 
 // A ticket for the parts of an asynchronous call.  Once 64 tickets are outstanding, those whose every part is
@@ -1764,6 +1776,54 @@ static int parts_wait(cv_ctx *ctx, const std::vector<Part> &parts) {
     return rc;
 }
 
+// The frame of a pipelined call over n records (or transactions): shard(device, b, e, packing threads, Part *) runs
+// over the shards dispatch cuts, an asynchronous shard recording its output in its Part.  A shard failed: the shards
+// that did enqueue are waited for here — nothing may read the caller's arrays or write its outputs after an
+// error return.  Else the ticket for the live parts, when one was asked for (0: nothing is in flight).
+template <class S>
+static int pipelined_call(cv_ctx *ctx, const Opts &o, size_t n, size_t align, uint64_t *ticket, S shard) {
+    std::vector<Part> parts(ctx->devs.size(), Part{UINT64_MAX, 0, 0});
+    const int rc = dispatch(ctx, o, n, align, [&](Device &d, size_t b, size_t e, int threads) {
+        return shard(d, b, e, threads, &parts[dev_index(ctx, d)]);
+    });
+    std::vector<Part> live;
+    for (const Part &p : parts)
+        if (p[0] != UINT64_MAX) live.push_back(p);
+    if (rc != CV_OK) {
+        (void)parts_wait(ctx, live);
+        return rc;
+    }
+    if (ticket) *ticket = live.empty() ? 0 : ticket_add(ctx, std::move(live));
+    return CV_OK;
+}
+
+// The options of a Merkle or transaction call: shards of whole transactions — the leaf work per transaction
+// (Σ blocks) decides, so a batch is cut by leaves, transaction counts scaled so each device gets ~1/k of the
+// leaves (C3: uniform; ~4,096 signatures' worth of transactions at its 8 per transaction).
+static Opts tx_opts(cv_ctx *ctx) {
+    Opts o = ctx->opts();
+    o.shard_min = std::max<size_t>(1, o.shard_min / 8);
+    o.spread_min = std::max<size_t>(1, o.spread_min / 8);
+    return o;
+}
+
+// Whether shard [t0, t1) of a synchronous Merkle or transaction call is small (one DMA, no pipeline frame):
+// its staging — the Merkle stage *st, planned here, plus `extra` bytes — is at most kMerkleSmall.  The records alone
+// (12 B per leaf, 4 per transaction) bound the staging from below, so a shard past kMerkleSmall by them skips the
+// range scan of its leaves (C3's 6M leaves: several ms on the synchronous call's critical path).  CV_E_ARGS: its
+// leaves reach past the arena, or an off + len wraps.
+static int merkle_small_gate(Device &d, int threads, const MerkleIn &in, size_t t0, size_t t1, size_t extra, MStage *st,
+                             WorkerPool **pool, bool *small) {
+    *small = false;
+    const size_t nlv = (size_t)in.txb[t1] - in.txb[t0];
+    if (nlv * 12 + (t1 - t0) * 4 + extra > kMerkleSmall) return CV_OK;
+    *pool = &d.workers(threads);
+    *st = mstage_plan(t0, t1, in.txb, in.off, in.len, *pool);
+    if (!mstage_in_bounds(*st, in.arena_bytes)) return CV_E_ARGS;
+    *small = st->total + extra <= kMerkleSmall;
+    return CV_OK;
+}
+
 // The keyed decision of the plain entry points: batches the tri-chain latency form takes (n <= tri_max)
 // stay on the plain path whatever their keys — there the per-signature chain is the latency, and the tri
 // chain beats the keyed comb chain (notary batch of 4,096 with 64 signers 0.47 vs 0.34 ms distinct).
@@ -1795,24 +1855,9 @@ static int verify_call(cv_ctx *ctx, size_t n, VerifyIn in, uint64_t *ticket) {
     const Opts o = ctx->opts();
     const bool async = ticket != nullptr;
     if (!in.keys && want_keyed(o, n, in.pk)) in.auto_keyed = true;
-    std::vector<Part> parts(ctx->devs.size(), Part{UINT64_MAX, 0, 0});
-    const int rc = dispatch(ctx, o, n, 64, [&](Device &d, size_t b, size_t e, int threads) {
-        Part p{UINT64_MAX, 0, 0};
-        const int r = verify_shard(ctx, d, o, b, e, in, threads, async, &p);
-        if (r == CV_OK && async && p[0] != UINT64_MAX) parts[dev_index(ctx, d)] = p;
-        return r;
+    return pipelined_call(ctx, o, n, 64, ticket, [&](Device &d, size_t b, size_t e, int threads, Part *part) {
+        return verify_shard(ctx, d, o, b, e, in, threads, async, part);
     });
-    std::vector<Part> live;
-    for (const Part &p : parts)
-        if (p[0] != UINT64_MAX) live.push_back(p);
-    if (rc != CV_OK) {
-        // a shard failed: the shards that did enqueue are waited for here — nothing may read the caller's
-        // arrays or write its bitmap after an error return
-        (void)parts_wait(ctx, live);
-        return rc;
-    }
-    if (async) *ticket = live.empty() ? 0 : ticket_add(ctx, std::move(live));
-    return CV_OK;
 }
 
 int cv_ed25519_verify_batch(cv_ctx *ctx, size_t n, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_arena,
@@ -1821,15 +1866,7 @@ int cv_ed25519_verify_batch(cv_ctx *ctx, size_t n, const uint8_t *pk, const uint
     if (!ctx) return CV_E_ARGS;
     if (n == 0) return CV_OK;
     if (!pk || !sig || !msg_off || !msg_len || !verdict_bitmap) return CV_E_ARGS;
-    VerifyIn in;
-    in.pk = pk;
-    in.sig = sig;
-    in.arena = msg_arena;
-    in.off = msg_off;
-    in.len = msg_len;
-    in.bitmap = verdict_bitmap;
-    in.status = status;
-    return verify_call(ctx, n, in, nullptr);
+    return verify_call(ctx, n, verify_in(pk, sig, msg_arena, msg_off, msg_len, verdict_bitmap, status), nullptr);
 }
 
 int cv_ed25519_verify_batch_async(cv_ctx *ctx, size_t n, const uint8_t *pk, const uint8_t *sig,
@@ -1839,15 +1876,7 @@ int cv_ed25519_verify_batch_async(cv_ctx *ctx, size_t n, const uint8_t *pk, cons
     *ticket = 0;
     if (n == 0) return CV_OK;
     if (!pk || !sig || !msg_off || !msg_len || !verdict_bitmap) return CV_E_ARGS;
-    VerifyIn in;
-    in.pk = pk;
-    in.sig = sig;
-    in.arena = msg_arena;
-    in.off = msg_off;
-    in.len = msg_len;
-    in.bitmap = verdict_bitmap;
-    in.status = status;
-    return verify_call(ctx, n, in, ticket);
+    return verify_call(ctx, n, verify_in(pk, sig, msg_arena, msg_off, msg_len, verdict_bitmap, status), ticket);
 }
 
 int cv_ed25519_verify_batch_ex(cv_ctx *ctx, size_t n, const uint8_t *pk, const uint8_t *sig, const uint8_t *msg_arena,
@@ -1857,14 +1886,7 @@ int cv_ed25519_verify_batch_ex(cv_ctx *ctx, size_t n, const uint8_t *pk, const u
     if (ticket) *ticket = 0;
     if (n == 0) return CV_OK;
     if (!pk || !sig || !msg_off || !msg_len || !verdict_bitmap) return CV_E_ARGS;
-    VerifyIn in;
-    in.pk = pk;
-    in.sig = sig;
-    in.arena = msg_arena;
-    in.off = msg_off;
-    in.len = msg_len;
-    in.bitmap = verdict_bitmap;
-    in.status = status;
+    VerifyIn in = verify_in(pk, sig, msg_arena, msg_off, msg_len, verdict_bitmap, status);
     in.arena_bytes = arena_bytes;
     return verify_call(ctx, n, in, ticket);
 }
@@ -1945,51 +1967,26 @@ static int merkle_call(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, const
         if (tx_leaf_begin[t + 1] < tx_leaf_begin[t]) return CV_E_ARGS;
     if (nleaves && (!leaf_off || !leaf_len)) return CV_E_ARGS;
     if (ntx > 0xfffffffeull || nleaves > 0xffffffffull) return CV_E_TOO_LARGE;
-    Opts o = ctx->opts();
-    // shards of whole transactions: the leaf work per transaction (Σ blocks) decides, so a batch is cut by
-    // leaves — transaction counts scaled so each device gets ~1/k of the leaves (C3: uniform)
-    o.shard_min = std::max<size_t>(1, o.shard_min / 8);          // ~4,096 signatures' worth of transactions
-    o.spread_min = std::max<size_t>(1, o.spread_min / 8);
+    const Opts o = tx_opts(ctx);
     MerkleIn in{leaf_arena, leaf_off, leaf_len, tx_leaf_begin, ids, tx_status, arena_bytes};
     {
         std::lock_guard<std::mutex> g(ctx->st_mu);
         ctx->stats.merkle_calls++;
     }
-    std::vector<Part> parts(ctx->devs.size(), Part{UINT64_MAX, 0, 0});
-    const int rc = dispatch(ctx, o, ntx, 1, [&](Device &d, size_t t0, size_t t1, int threads) {
+    return pipelined_call(ctx, o, ntx, 1, ticket, [&](Device &d, size_t t0, size_t t1, int threads, Part *part) {
         if (t1 <= t0) return CV_OK;
         CV_TRY(hipSetDevice(d.ordinal));
-        // small synchronous shards: one DMA, no pipeline frame.  Their records alone (12 B per leaf, 4 per
-        // transaction) bound the staging from below, so a shard past kMerkleSmall by them skips the range scan
-        // of its leaves (C3's 6M leaves: several ms on the synchronous call's critical path)
-        const size_t nlv = (size_t)tx_leaf_begin[t1] - tx_leaf_begin[t0];
-        if (!ticket && nlv * 12 + (t1 - t0) * 4 <= kMerkleSmall) {
-            WorkerPool *pool = &d.workers(threads);
-            const MStage st = mstage_plan(t0, t1, tx_leaf_begin, leaf_off, leaf_len, pool);
-            if (!mstage_in_bounds(st, in.arena_bytes)) return CV_E_ARGS;   // past the arena, or off + len wraps
-            if (st.total <= kMerkleSmall) return merkle_shard_small(d, st, in, pool);
+        if (!ticket) {
+            MStage st;
+            WorkerPool *pool = nullptr;
+            bool small = false;
+            const int r = merkle_small_gate(d, threads, in, t0, t1, 0, &st, &pool, &small);
+            if (r != CV_OK) return r;
+            if (small) return merkle_shard_small(d, st, in, pool);
         }
-        int k = 0, r = CV_OK;
-        std::unique_lock<std::mutex> lk;
-        PipeOut &po = pipe_out(d, &k, lk);
-        r = merkle_enqueue(ctx, d, o, po, t0, t1, in, threads);
-        if (r != CV_OK) return r;
-        if (ticket) {
-            parts[dev_index(ctx, d)] = {(uint64_t)dev_index(ctx, d), (uint64_t)k, po.gen};
-            po.ticketed = true;
-            return CV_OK;
-        }
-        return pipe_finish(d, po);
+        return shard_pipelined(ctx, d, ticket != nullptr, part,
+                               [&](PipeOut &po) { return merkle_enqueue(ctx, d, o, po, t0, t1, in, threads); });
     });
-    std::vector<Part> live;
-    for (const Part &p : parts)
-        if (p[0] != UINT64_MAX) live.push_back(p);
-    if (rc != CV_OK) {
-        (void)parts_wait(ctx, live);
-        return rc;
-    }
-    if (ticket) *ticket = live.empty() ? 0 : ticket_add(ctx, std::move(live));
-    return CV_OK;
 }
 
 int cv_merkle_tx_ids_ex(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, const uint64_t *leaf_off,
@@ -2052,11 +2049,7 @@ static int txs_shard_small(Device &d, const Opts &o, const MStage &st, const TxI
     uint64_t *doff = reinterpret_cast<uint64_t *>(dout + o_off);
     uint32_t *dlen = reinterpret_cast<uint32_t *>(dout + o_len);
     uint64_t *dbm = reinterpret_cast<uint64_t *>(dout + o_bm);
-    CV_TRY(ws_begin(d, sl, s));
-    const hipError_t ek = launch_merkle(st, dv, sl.mdig.as<uint32_t>(), dout, dout + o_mst, s);
-    const hipError_t e2 = ws_end(sl, s);
-    CV_TRY(ek);
-    CV_TRY(e2);
+    CV_TRY(ws_run(d, sl, s, [&] { return launch_merkle(st, dv, sl.mdig.as<uint32_t>(), dout, dout + o_mst, s); }));
     if (ns) {
         CV_TRY(cvk_tx_sig_refs((uint32_t)ns, 0, (uint32_t)nt, (uint32_t)s0, dtsb, doff, dlen, s));
         CV_TRY(launch_verify(d, o.plan, sl, (uint32_t)ns, dv + o_pk, dv + o_sig, dout, doff, dlen, dbm,
@@ -2089,56 +2082,29 @@ static int txs_call(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, const ui
     if (nleaves && (!leaf_off || !leaf_len)) return CV_E_ARGS;
     if (nsig && (!pk || !sig)) return CV_E_ARGS;
     if (ntx > 0xfffffffeull) return CV_E_TOO_LARGE;
-    Opts o = ctx->opts();
-    // shards of whole transactions, scaled as merkle_call's (~4,096 signatures' worth at C3's 8 per transaction)
-    o.shard_min = std::max<size_t>(1, o.shard_min / 8);
-    o.spread_min = std::max<size_t>(1, o.spread_min / 8);
+    const Opts o = tx_opts(ctx);
     TxIn in{{leaf_arena, leaf_off, leaf_len, tx_leaf_begin, ids, tx_status, arena_bytes}, pk, sig, tx_sig_begin, sig_status,
             tx_ok, now_s()};
     {
         std::lock_guard<std::mutex> g(ctx->st_mu);
         ctx->stats.merkle_calls++;
     }
-    std::vector<Part> parts(ctx->devs.size(), Part{UINT64_MAX, 0, 0});
-    const int rc = dispatch(ctx, o, ntx, 1, [&](Device &d, size_t t0, size_t t1, int threads) {
+    return pipelined_call(ctx, o, ntx, 1, ticket, [&](Device &d, size_t t0, size_t t1, int threads, Part *part) {
         if (t1 <= t0) return CV_OK;
         CV_TRY(hipSetDevice(d.ordinal));
-        // small synchronous shards: one DMA, one stream (the records alone bound the staging from below: a shard
-        // past kMerkleSmall by them skips the range scan of its leaves, as merkle_call)
-        const size_t nlv = (size_t)tx_leaf_begin[t1] - tx_leaf_begin[t0];
-        const size_t ns = tx_sig_begin[t1] - tx_sig_begin[t0];
-        if (!ticket && nlv * 12 + (t1 - t0) * 4 + ns * 96 <= kMerkleSmall) {
-            WorkerPool *pool = &d.workers(threads);
-            const MStage st = mstage_plan(t0, t1, tx_leaf_begin, leaf_off, leaf_len, pool);
-            if (!mstage_in_bounds(st, in.m.arena_bytes)) return CV_E_ARGS;   // past the arena, or off + len wraps
-            if (st.total + ns * 96 <= kMerkleSmall) return txs_shard_small(d, o, st, in, pool);
+        if (!ticket) {   // (extra: the shard's keys and signatures)
+            MStage st;
+            WorkerPool *pool = nullptr;
+            bool small = false;
+            const size_t ns = tx_sig_begin[t1] - tx_sig_begin[t0];
+            const int r = merkle_small_gate(d, threads, in.m, t0, t1, ns * 96, &st, &pool, &small);
+            if (r != CV_OK) return r;
+            if (small) return txs_shard_small(d, o, st, in, pool);
         }
-        int k = 0, r = CV_OK;
-        std::unique_lock<std::mutex> lk;
-        PipeOut &po = pipe_out(d, &k, lk);
-        r = txs_enqueue(ctx, d, o, po, t0, t1, in, threads, ticket != nullptr);
-        if (r != CV_OK) return r;
-        if (ticket) {
-            parts[dev_index(ctx, d)] = {(uint64_t)dev_index(ctx, d), (uint64_t)k, po.gen};
-            po.ticketed = true;
-            return CV_OK;
-        }
-        const double ts = now_s();
-        r = pipe_finish(d, po);
-        std::lock_guard<std::mutex> g(ctx->st_mu);
-        ctx->stats.pipe[4] += now_s() - ts;
-        timeline_account(ctx, po);
-        return r;
+        return shard_pipelined(ctx, d, ticket != nullptr, part, [&](PipeOut &po) {
+            return txs_enqueue(ctx, d, o, po, t0, t1, in, threads, ticket != nullptr);
+        });
     });
-    std::vector<Part> live;
-    for (const Part &p : parts)
-        if (p[0] != UINT64_MAX) live.push_back(p);
-    if (rc != CV_OK) {
-        (void)parts_wait(ctx, live);
-        return rc;
-    }
-    if (ticket) *ticket = live.empty() ? 0 : ticket_add(ctx, std::move(live));
-    return CV_OK;
 }
 
 int cv_verify_transactions(cv_ctx *ctx, size_t ntx, const uint8_t *leaf_arena, const uint64_t *leaf_off,

@@ -11,6 +11,7 @@
 //   pipe_cuts            the host pipeline's sub-chunk plan (64-aligned, covering, balanced tail)
 //   merkle_cuts          the Merkle sub-chunk plan (whole transactions, leaf targets, ramp, 32-bit clamp)
 //   dispatch             routing: shard ranges over k devices, per-device exclusion, concurrent callers
+//   pipelined_call       the call frame: a failed shard's siblings are waited for, no ticket; else one ticket
 //   mstage_plan/_pack    Merkle staging of a transaction range (non-monotone offsets, empty txs, compact)
 //   cv_tx_verdicts       per-transaction AND
 //   cv_batch.h           what the one-shot batch calls share: Layout against the chained al16 forms, both ranges_ok,
@@ -563,6 +564,63 @@ static void test_failed_finish_reaches_waiter() {
     ctx.devs.clear();
 }
 
+// The call frame (pipelined_call) on the host: a call cut over two devices whose shard on device 1 fails is waited
+// for on device 0 (its output no longer pending) and hands out no ticket; when both shards enqueue, one ticket
+// whose cv_wait returns the parts' result, once.  Device ordinal 4095 does not exist, so every finish fails at
+// hipSetDevice (as test_failed_finish_reaches_waiter).
+static void test_pipelined_call() {
+    cv_ctx ctx;
+    for (int k = 0; k < 2; k++) {
+        ctx.devs.emplace_back(new Device());
+        ctx.devs.back()->ordinal = 4095;
+    }
+    ctx.opt[CV_OPT_SHARD_MIN].store(64);
+    ctx.opt[CV_OPT_SPREAD_MIN].store(128);
+    const Opts o = ctx.opts();
+    std::atomic<int> shards{0};
+    // a shard that marks its device's next output pending and ticketed, as an asynchronous enqueue leaves it
+    auto enqueue = [&](Device &d, size_t b, size_t e, Part *part) {
+        shards++;
+        CHECK(e > b && b % 64 == 0);
+        int k = -1;
+        std::unique_lock<std::mutex> lk;
+        PipeOut &po = pipe_out(d, &k, lk);
+        po.pending = true;
+        po.ticketed = true;
+        po.gen++;
+        *part = {(uint64_t)dev_index(&ctx, d), (uint64_t)k, po.gen};
+        return CV_OK;
+    };
+    // ---- the error run
+    uint64_t ticket = 0;
+    int rc = pipelined_call(&ctx, o, 256, 64, &ticket, [&](Device &d, size_t b, size_t e, int, Part *part) {
+        if (dev_index(&ctx, d) == 1) {
+            shards++;
+            return CV_E_ARGS;
+        }
+        return enqueue(d, b, e, part);
+    });
+    CHECK(shards.load() == 2);                             // n = 256 was cut over both devices
+    CHECK(rc == CV_E_ARGS);
+    for (PipeOut &po : ctx.devs[0]->out) CHECK(!po.pending);   // device 0's shard was waited for
+    CHECK(ticket == 0);
+    CHECK(ctx.tickets.empty() && ctx.tickets_done.empty());
+    // ---- the success run
+    shards = 0;
+    ticket = 0;
+    rc = pipelined_call(&ctx, o, 256, 64, &ticket,
+                        [&](Device &d, size_t b, size_t e, int, Part *part) { return enqueue(d, b, e, part); });
+    CHECK(rc == CV_OK && shards.load() == 2);
+    CHECK(ticket != 0 && ctx.tickets.size() == 1 && ctx.tickets.begin()->second.size() == 2);
+    CHECK(cv_wait(&ctx, ticket) == CV_E_HIP);              // the parts' result: both finishes fail
+    for (auto &d : ctx.devs)
+        for (PipeOut &po : d->out) CHECK(!po.pending);
+    CHECK(cv_wait(&ctx, ticket) == CV_E_ARGS);             // a ticket is waited once
+    CHECK(ctx.tickets.empty());
+    for (auto &d : ctx.devs) CHECK(d->load.load() == 0);
+    ctx.devs.clear();
+}
+
 static void test_abi_guards() {
     cv_ctx *ctx = nullptr;
     CHECK(cv_open(0, nullptr) == CV_E_ARGS);
@@ -583,6 +641,7 @@ int main(int argc, char **argv) {
     for (int threads : {1, 2, 5}) test_pack(threads);
     for (size_t ndev : {1ul, 2ul, 3ul, 8ul}) test_dispatch(ndev, 1, 60);
     test_dispatch(4, 4, 200);        // 4 threads x 200 interleaved calls, 4 devices
+    test_pipelined_call();           // (device 1's shard runs on its worker thread)
     if (!threads_only) {
         test_dedupe();
         test_layout();

@@ -569,3 +569,108 @@ def test_bounded_calls_one_byte_short_touch_nothing(engine, vbatches, tx_case):
     for name in g.order:
         assert g.untouched(name), name
     g.check_guards("bounded Merkle calls")
+
+
+def _ascending_batch(corpus, n):
+    """n corpus records whose messages are laid out one after another (a spare byte between them), so the offsets
+    ascend and the LAST record reaches farthest: an arena one byte short fails in a call's last sub-chunk."""
+    rows = corpus_rows(corpus, n, "accepted", seed=3)
+    lens = _c(corpus["len"][rows], np.uint32)
+    off = np.zeros(n, np.uint64)
+    off[1:] = np.cumsum(lens[:-1].astype(np.uint64) + 1)
+    arena = np.full(int(off[-1]) + int(lens[-1]), 0xEE, np.uint8)
+    for o, l, s in zip(off, lens, corpus["off"][rows]):
+        arena[int(o):int(o) + int(l)] = corpus["arena"][int(s):int(s) + int(l)]
+    assert (off[:-1] + lens[:-1] < off[-1]).all()
+    return dict(n=n, pk=_c(corpus["pk"][rows], np.uint8), sig=_c(corpus["sig"][rows], np.uint8), arena=arena, off=off,
+                len=lens, verdict=corpus["verdict"][rows].astype(bool), status=corpus["status"][rows].astype(np.uint8))
+
+
+def _verify_short_then_exact(eng, v, a, with_untouched, what):
+    """cv_ed25519_verify_batch_ex with the arena one byte short (no ticket, then a ticket): CV_E_ARGS, ticket 0 and —
+    with_untouched — no output byte written; then the whole arena: the batch's verdicts and status bytes."""
+    lib, h, n = eng._lib, eng._h, v["n"]
+    extent = int(lib.cv_msg_extent(n, _p(a["off"]), _p(a["len"])))
+    assert extent == a["arena"].size == int(v["off"][-1]) + int(v["len"][-1])
+    g = _verify_outputs(eng, n, True, 0xA5, False)
+
+    def call(arena_bytes, ticket):
+        return lib.cv_ed25519_verify_batch_ex(h, n, _p(a["pk"]), _p(a["sig"]), _p(a["arena"]), arena_bytes, _p(a["off"]),
+                                              _p(a["len"]), g.ptr("bitmap"), g.ptr("status"), ticket)
+
+    for with_ticket in (False, True):
+        t = ctypes.c_uint64(99)
+        assert call(extent - 1, ctypes.byref(t) if with_ticket else None) == CV_E_ARGS, (what, with_ticket)
+        if with_ticket:
+            assert t.value == 0, what
+        if with_untouched:
+            assert g.untouched("bitmap") and g.untouched("status"), (what, with_ticket)
+        g.check_guards(f"{what} short, ticket={with_ticket}")
+        g.refill()
+        t = ctypes.c_uint64(0)
+        assert call(extent, ctypes.byref(t) if with_ticket else None) == 0, (what, with_ticket)
+        assert lib.cv_wait(h, t) == 0, what
+        bm = g.read("bitmap", np.uint64)
+        assert np.array_equal(native.bitmap_to_bools(bm, n), v["verdict"]), (what, with_ticket)
+        assert tail_bits(bm, n) == 0, what
+        assert np.array_equal(g.read("status"), v["status"]), (what, with_ticket)
+        g.check_guards(f"{what} exact, ticket={with_ticket}")
+        g.refill()
+
+
+def test_bounded_calls_fail_inside_the_pipeline(engine, corpus, tx_case):
+    """The CV_E_ARGS returns of the bounded calls from INSIDE the host pipeline (the one-byte-short test above only
+    reaches the small paths): the arena one byte short of what the LAST record (leaf) reaches, and options under
+    which the call has many sub-chunks, so the earlier ones are already enqueued when the last one is refused.  The
+    call drains them, returns CV_E_ARGS with ticket 0 and writes no output byte; the same call with the whole arena
+    then gives the exact results — the input ring, the staging blocks and the outputs were left usable.  Verify
+    with and without a ticket, pageable and pinned arrays; Merkle ids and transactions in their asynchronous forms
+    (at this size only those reach the pipeline); and the verify call cut over two virtual devices, where the shard
+    that succeeded may have delivered its words, so only the return, the ticket and the next call are checked."""
+    v = _ascending_batch(corpus, 1000)
+    arrays = {k: v[k] for k in ("pk", "sig", "arena", "off", "len")}
+    pipe = dict(pipe_min=64, pipe_first=64, pipe_chunk=128, auto_keyed=0)       # 1,000 records: >= 8 sub-chunks
+    with Options(engine, **pipe):
+        for pinned in (False, True):
+            a = {k: engine.host_copy(x) for k, x in arrays.items()} if pinned else arrays
+            _verify_short_then_exact(engine, v, a, True, f"verify pinned={pinned}")
+    # ---- Merkle ids and transactions, asynchronous
+    lib, h, c = engine._lib, engine._h, tx_case
+    ntx, nsig = c["ntx"], c["nsig"]
+    lin = (_p(c["off"]), _p(c["len"]), _p(c["begin"]))
+    sizes = [("ids", 32 * ntx, 1), ("tx_status", ntx, 1), ("sig_status", nsig, 1), ("tx_ok", ntx, 1)]
+
+    def merkle(g, arena_bytes, t):
+        return lib.cv_merkle_tx_ids_bounded(h, ntx, _p(c["arena"]), arena_bytes, *lin, g.ptr("ids"), g.ptr("tx_status"),
+                                            ctypes.byref(t))
+
+    def txs(g, arena_bytes, t):
+        return lib.cv_verify_transactions_ex(h, ntx, _p(c["arena"]), arena_bytes, *lin, _p(c["pk"]), _p(c["sig"]),
+                                             _p(c["tsb"]), g.ptr("ids"), g.ptr("tx_status"), g.ptr("sig_status"),
+                                             g.ptr("tx_ok"), ctypes.byref(t))
+
+    with Options(engine, merkle_chunk=1, pipe_first=64, pipe_chunk=128):
+        for name, call in (("merkle", merkle), ("transactions", txs)):
+            g = Guarded(sizes, 0xA5)
+            t = ctypes.c_uint64(99)
+            assert call(g, c["arena"].size - 1, t) == CV_E_ARGS, name   # the arena ends with the last leaf's last byte
+            assert t.value == 0, name
+            for out in g.order:
+                assert g.untouched(out), (name, out)
+            g.check_guards(f"{name} short")
+            t = ctypes.c_uint64(0)
+            assert call(g, c["arena"].size, t) == 0, name
+            assert lib.cv_wait(h, t) == 0, name
+            assert np.array_equal(g.read("ids", shape=(ntx, 32)), c["ids"]), name
+            assert np.array_equal(g.read("tx_status"), c["st"]), name
+            if name == "transactions":
+                assert np.array_equal(g.read("sig_status"), c["sst"]), name
+                assert np.array_equal(g.read("tx_ok"), c["ok"]), name
+            else:
+                assert g.untouched("sig_status") and g.untouched("tx_ok")
+            g.check_guards(f"{name} exact")
+    # ---- the verify call cut over two virtual devices: the second shard holds the last record
+    with native.Engine(1, virtual_devices=2) as e2:
+        with Options(e2, shard_min=64, spread_min=64, **pipe):
+            _verify_short_then_exact(e2, v, arrays, False, "verify, two virtual devices")
+            assert e2.stats("route")["split_calls"] == 4                       # every call was cut over both
