@@ -4,4 +4,4 @@ PublicKey.verifyWithECDSA / WireTransaction.id).  See DESIGN.md and include/cord
 
 from . import native  # noqa: F401
 
-__all__ = ["native", "crypto", "transactions", "notary", "workload"]
+__all__ = ["native", "crypto", "transactions", "notary", "workload", "keys"]

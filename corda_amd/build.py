@@ -25,9 +25,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # kernel translation units (cv_kcommon.h) compile in parallel; cv_kernels.hip holds the launchers
 SOURCES = ["cv_k_hs.hip", "cv_k_hss.hip", "cv_k_lat.hip", "cv_k_keyed.hip", "cv_k_misc.hip", "cv_k_sign.hip",
            "cv_k_pmt.hip", "cv_k_uniq.hip", "cv_k_ck.hip", "cv_k_notary.hip", "cv_k_tearoff.hip", "cv_k_resolve.hip",
-           "cv_k_dedupe.hip", "cv_k_hotkeys.hip",
+           "cv_k_dedupe.hip", "cv_k_hotkeys.hip", "cv_k_keystore.hip",
            "cv_kernels.hip", "cv_api.cpp", "cv_api_sign.cpp", "cv_api_pmt.cpp", "cv_api_uniq.cpp", "cv_api_ck.cpp",
-           "cv_api_notary.cpp", "cv_api_tearoff.cpp", "cv_api_resolve.cpp", "cv_api_dedupe.cpp", "cv_api_hotkeys.cpp"]
+           "cv_api_notary.cpp", "cv_api_tearoff.cpp", "cv_api_resolve.cpp", "cv_api_dedupe.cpp", "cv_api_hotkeys.cpp",
+           "cv_api_keystore.cpp"]
 # host symbols hidden: the library exports only the cv_* entry points include/cordaverify.h declares
 # (cv_host.h gives the header's declarations default visibility); the cvk_* launchers stay internal
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",

@@ -15,6 +15,8 @@
 //   cv_k_resolve.hip the graph steps of cv_resolve_batch (cv_resolve.h): join-table insert, probe, gate
 //   cv_k_dedupe.hip  the device key dedupe (cv_keydedupe.h): insert, mark, count, scan, emit
 //   cv_k_hotkeys.hip the hot-key route (cv_hotkeys.h): tally, classify, keys, flag, gather, merge
+//   cv_k_keystore.hip the device key store (cv_keystore.h): expand, classify, put, lookup, rehash, the transactions'
+//                  gate, many-key signing
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +31,7 @@
 #include "cv_resolve.h"
 #include "cv_keydedupe.h"
 #include "cv_hotkeys.h"
+#include "cv_keystore.h"
 
 #define CV_BLOCK 256
 // waves per SIMD the throughput Straus kernel is built for (its __launch_bounds__; 168 VGPRs fit 3).  A build
@@ -220,6 +223,14 @@ __global__ void cv_hot_keys_kernel(CvHot H);
 __global__ void cv_hot_flag_kernel(CvHot H);
 __global__ void cv_hot_gather_kernel(CvHot H);
 __global__ void cv_hot_merge_kernel(CvHot H, uint64_t *bitmap, uint8_t *status);
+// the device key store (cv_k_keystore.hip, cv_keystore.h); an add's grouping is cv_dedupe_insert_kernel
+__global__ void cv_ks_expand_kernel(uint32_t n, const uint8_t *seed, uint32_t *rec, uint32_t *pk);
+__global__ void cv_ks_classify_kernel(CvKeyTable T, CvDedupe D, uint8_t *status, uint32_t *dstat);
+__global__ void cv_ks_put_kernel(CvKeyTable T, CvDedupe D, const uint32_t *rec, const uint8_t *status, uint32_t *dstat);
+__global__ void cv_ks_lookup_kernel(CvKeyTable T, uint32_t n, const uint32_t *pk, uint32_t *slot, uint8_t *flag, uint8_t present, uint32_t *dstat);
+__global__ void cv_ks_rehash_kernel(CvKeyTable from, CvKeyTable to, uint32_t *dstat);
+__global__ void cv_ks_tx_gate_kernel(CvKeyTable T, CvKeyTx X);
+__global__ void cv_ks_sign_kernel(CvKeyTable T, uint32_t n, const uint32_t *slot, const uint8_t *arena, const uint64_t *off, const uint32_t *len, uint8_t *sig_out, const uint32_t *bw16);
 __global__ void cv_mad_bench_kernel(uint32_t iters, uint64_t *out);
 __global__ void cv_femul_bench_kernel(uint32_t iters, int32_t *out);
 __global__ void cv_mad_clock_kernel(uint32_t iters, uint64_t *out);

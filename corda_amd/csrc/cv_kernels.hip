@@ -550,6 +550,57 @@ hipError_t cvk_uniq_snapshot(const CvUniqTable *T, const CvUniqSnap *S, uint32_t
     return hipGetLastError();
 }
 
+// ---- the device key store (cv_keystore.h).  Grids of one lane per record / key / slot / transaction.
+hipError_t cvk_ks_add(const CvKeyTable *T, const CvDedupe *D, uint8_t *seed, uint32_t *rec, uint8_t *status,
+                      uint32_t *dstat, hipStream_t stream) {
+    if (!T || !D || D->n == 0 || !seed || !rec || !status || !dstat) return hipErrorInvalidValue;
+    const dim3 grid = uniq_grid(D->n), block(CV_BLOCK);
+    hipLaunchKernelGGL(cv_ks_expand_kernel, grid, block, 0, stream, D->n, (const uint8_t *)seed, rec,
+                       const_cast<uint32_t *>(D->pk));
+    hipError_t e = hipMemsetAsync(seed, 0, 32 * (size_t)D->n, stream);
+    if (e != hipSuccess) return e;
+    // the table and, right behind it, stat: empty slots and STAT_OK in one fill
+    e = hipMemsetAsync(D->tab, 0xff, 4 * (size_t)(D->mask + 1) + 4 * CVD_STAT_WORDS, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cv_dedupe_insert_kernel, grid, block, 0, stream, *D);
+    hipLaunchKernelGGL(cv_ks_classify_kernel, grid, block, 0, stream, *T, *D, status, dstat);
+    hipLaunchKernelGGL(cv_ks_put_kernel, grid, block, 0, stream, *T, *D, (const uint32_t *)rec, (const uint8_t *)status,
+                       dstat);
+    return hipGetLastError();
+}
+
+hipError_t cvk_ks_lookup(const CvKeyTable *T, uint32_t n, const uint32_t *pk, uint32_t *slot, uint8_t *flag,
+                         uint8_t present, uint32_t *dstat, hipStream_t stream) {
+    if (!T || n == 0 || !pk || !dstat) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_ks_lookup_kernel, uniq_grid(n), dim3(CV_BLOCK), 0, stream, *T, n, pk, slot, flag, present, dstat);
+    return hipGetLastError();
+}
+
+hipError_t cvk_ks_rehash(const CvKeyTable *from, const CvKeyTable *to, uint32_t *dstat, hipStream_t stream) {
+    if (!from || !to || !dstat) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_ks_rehash_kernel, uniq_grid((uint64_t)from->mask + 1), dim3(CV_BLOCK), 0, stream, *from, *to,
+                       dstat);
+    return hipGetLastError();
+}
+
+hipError_t cvk_ks_tx_gate(const CvKeyTable *T, const CvKeyTx *X, hipStream_t stream) {
+    if (!T || !X || X->ntx == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cv_ks_tx_gate_kernel, uniq_grid(X->ntx), dim3(CV_BLOCK), 0, stream, *T, *X);
+    return hipGetLastError();
+}
+
+// n signatures, each with the record of its slot; [r]B from the device's CV_BW16 rows, as cvk_sign_keyed
+hipError_t cvk_ks_sign(const CvKeyTable *T, uint32_t n, const uint32_t *slot, const uint8_t *arena, const uint64_t *off,
+                       const uint32_t *len, uint8_t *sig, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (!T || !slot) return hipErrorInvalidValue;
+    const uint32_t *bw16 = nullptr;
+    const hipError_t e = bw16_table(&bw16, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(cv_ks_sign_kernel, uniq_grid(n), dim3(CV_BLOCK), 0, stream, *T, n, slot, arena, off, len, sig, bw16);
+    return hipGetLastError();
+}
+
 // Leaf hashing: balanced pairs (round 3: 2.58 -> 2.47 ms per 1M C3 txs against the length-sorted passes,
 // profiles/r03a_ab_leaf_mode.log), then one lane per transaction for the tree.
 hipError_t cvk_merkle(uint32_t ntx, uint32_t nleaves, uint32_t leaf_base, const uint8_t *arena, const uint64_t *leaf_off,

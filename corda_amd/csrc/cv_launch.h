@@ -9,6 +9,7 @@
 #include "cv_tearoff.h"
 #include "cv_keydedupe.h"
 #include "cv_hotkeys.h"
+#include "cv_keystore.h"
 #include "cv_resolve.h"
 #include "cv_uniq.h"
 
@@ -144,6 +145,24 @@ hipError_t cvk_dedupe(const CvDedupe *D, uint32_t *const *sums, hipStream_t stre
 hipError_t cvk_hotkeys_front(const CvHot *H, uint32_t *const *sums, hipStream_t stream);
 hipError_t cvk_hotkeys_gather(const CvHot *H, hipStream_t stream);
 hipError_t cvk_hotkeys_merge(const CvHot *H, uint64_t *bitmap, uint8_t *status, hipStream_t stream);
+// The device key store (cv_keystore.h; kernels in cv_k_keystore.hip), every step enqueued on `stream`, nothing
+// synchronised.  dstat: CKS_D_WORDS counters, zeroed by the caller.
+//   add    : n seeds -> the staged records rec (n * CKS_REC_WORDS words) and D->pk (n * 8 words, the call's pk_out);
+//            the seeds are cleared behind the expansion; then the call-local grouping over D (its table and stat
+//            lie together as cvd_layout places them: one memset of 0xff), classify -> status[n], put.  The caller
+//            clears rec behind it.
+//   lookup : per key its slot (optional) and flag (optional: `present` for a resident key, else 1 - present)
+//   rehash : one lane per slot of `from` re-inserts into `to` (occ of `to` zero before)
+//   tx_gate: one lane per transaction -> X->slot / off / len per key, tx_status, first_bad
+//   sign   : n signatures, record i with the key in slot[i]; CKS_NONE gives 64 zero bytes
+hipError_t cvk_ks_add(const CvKeyTable *T, const CvDedupe *D, uint8_t *seed, uint32_t *rec, uint8_t *status,
+                      uint32_t *dstat, hipStream_t stream);
+hipError_t cvk_ks_lookup(const CvKeyTable *T, uint32_t n, const uint32_t *pk, uint32_t *slot, uint8_t *flag,
+                         uint8_t present, uint32_t *dstat, hipStream_t stream);
+hipError_t cvk_ks_rehash(const CvKeyTable *from, const CvKeyTable *to, uint32_t *dstat, hipStream_t stream);
+hipError_t cvk_ks_tx_gate(const CvKeyTable *T, const CvKeyTx *X, hipStream_t stream);
+hipError_t cvk_ks_sign(const CvKeyTable *T, uint32_t n, const uint32_t *slot, const uint8_t *arena, const uint64_t *off,
+                       const uint32_t *len, uint8_t *sig, hipStream_t stream);
 // Merkle ids of ntx transactions whose leaves are nleaves records starting at leaf index leaf_base:
 // leaf_off / leaf_len index the records (leaf i of the call = record i), tx_begin[0..ntx] holds absolute
 // leaf indices (tx_begin[0] >= leaf_base), leaf_digest is nleaves * 32 bytes of workspace.

@@ -53,6 +53,16 @@ TS_NO_LEAF = 0xFFFFFFFF
 NS_NO_SIG = 0xFFFFFFFF            # first_bad: no signature of the transaction settled its outcome
 NS_PRE_SIGNATURE, NS_PRE_KEY = 1, 2   # sig_pre: the host prefilter's SignatureException / InvalidKeyException
 CK_WIDE_DEFAULT, CK_WIDE_ALWAYS, CK_WIDE_NEVER = 0, 1, 0xFFFFFFFF      # cv_missing_signers' wide_min
+CV_KS_ADDED = 0
+CV_KS_PRESENT = 1
+CV_KS_OK = 0
+CV_KS_NO_KEY = 1
+CV_ST_OK = 0
+CV_ST_NO_KEY = 1
+CV_ST_ALREADY_SIGNED = 2
+CV_ST_EMPTY = 3
+ST_NO_BAD = 0xFFFFFFFF            # first_bad of a CV_ST_OK transaction
+CV_KS_STATS = ("resident", "capacity", "slots", "probe")   # CV_KS_STAT_*
 CV_UNIQ_STATS = ("resident", "capacity", "slots", "rounds", "tail", "probe", "wraps")   # CV_UNIQ_STAT_*
 
 # every symbol include/cordaverify.h declares (tests check the library exports all of them)
@@ -74,6 +84,8 @@ EXPORTED = (
     "cv_notarise_batch", "cv_filtered_verify", "cv_tearoff_sign_batch", "cv_resolve_batch",
     "cv_ed25519_dedupe_keys_device", "cv_ed25519_dedupe_keys_workspace",
     "cv_ed25519_verify_device_hotkeys", "cv_ed25519_verify_hotkeys_workspace",
+    "cv_keystore_open", "cv_keystore_close", "cv_keystore_reserve", "cv_keystore_add", "cv_keystore_contains",
+    "cv_keystore_sign", "cv_keystore_stats", "cv_sign_transactions",
 )
 
 # cv_set_option names (include/cordaverify.h CV_OPT_*)
@@ -262,6 +274,23 @@ def load():
             lib.cv_ed25519_verify_device_hotkeys.restype = ctypes.c_int
             lib.cv_ed25519_verify_hotkeys_workspace.argtypes = [_sz]
             lib.cv_ed25519_verify_hotkeys_workspace.restype = ctypes.c_uint64
+        if hasattr(lib, "cv_keystore_open"):
+            lib.cv_keystore_open.argtypes = [_vp, ctypes.c_int, _sz, ctypes.POINTER(_vp)]
+            lib.cv_keystore_open.restype = ctypes.c_int
+            lib.cv_keystore_close.argtypes = [_vp]
+            lib.cv_keystore_close.restype = None
+            lib.cv_keystore_reserve.argtypes = [_vp, _sz]
+            lib.cv_keystore_reserve.restype = ctypes.c_int
+            lib.cv_keystore_add.argtypes = [_vp, _sz, _vp, _vp, _vp]
+            lib.cv_keystore_add.restype = ctypes.c_int
+            lib.cv_keystore_contains.argtypes = [_vp, _sz, _vp, _vp]
+            lib.cv_keystore_contains.restype = ctypes.c_int
+            lib.cv_keystore_sign.argtypes = [_vp, _sz, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]
+            lib.cv_keystore_sign.restype = ctypes.c_int
+            lib.cv_keystore_stats.argtypes = [_vp, _vp, _sz]
+            lib.cv_keystore_stats.restype = ctypes.c_int
+            lib.cv_sign_transactions.argtypes = [_vp, _vp, _sz, _vp, ctypes.c_uint64, _vp, _vp, _vp, _sz] + [_vp] * 6
+            lib.cv_sign_transactions.restype = ctypes.c_int
         lib.cv_calibrate.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         lib.cv_calibrate.restype = ctypes.c_int
         lib.cv_calibrate_cycles.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -1062,6 +1091,113 @@ class Signer:
             raise ValueError("the signer is closed")
         _check(self._lib.cv_ed25519_sign_keyed_device(self._engine._h, device, self._h, n, d_arena, d_off, d_len,
                                                       d_sig, stream or None), "cv_ed25519_sign_keyed_device")
+
+
+class KeyStore:
+    """A device-resident store of expanded private keys addressed by public key, bound to an engine (cv_keystore): the
+    node's KeyManagementService (Services.kt:206-219, PersistentKeyManagementService.kt:40-66) — add() is freshKey() for
+    a batch of seeds, contains() is keys.contains, sign() is KeyPair(pk, toPrivate(pk)).signWithECDSA with every record
+    naming its own key, sign_transactions() the builder's signing step (TransactionBuilder.kt:93-98,132-141) for a
+    batch.  No call gives out a private half.  Calls serialise on the store's own lock.  close() (or the
+    with-statement) overwrites and frees the table; the engine closes the stores still open when it is closed itself."""
+
+    def __init__(self, engine: Engine, capacity: int, device: int = 0):
+        self._engine = engine
+        self._lib = engine._lib
+        h = _vp()
+        _check(self._lib.cv_keystore_open(engine._h, device, int(capacity), ctypes.byref(h)), "cv_keystore_open")
+        self._h = h
+        engine._signers.add(self)
+
+    def close(self):
+        if self._h:
+            self._lib.cv_keystore_close(self._h)
+            self._h = None
+            self._engine._signers.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("the key store is closed")
+        return self._h
+
+    def add(self, seeds):
+        """cv_keystore_add: seeds (n,32) u8 -> (pk (n,32) u8, status u8[n]: CV_KS_ADDED | CV_KS_PRESENT).  CvError with
+        code -4 when resident + n would pass the capacity: nothing changed, reserve() first."""
+        h = self._open()
+        seeds = _u8(seeds).reshape(-1)
+        if seeds.size % 32:
+            raise ValueError("seeds must be n x 32 bytes")
+        n = seeds.size // 32
+        pk, st = np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8)
+        _check(self._lib.cv_keystore_add(h, n, _p(seeds) if n else None, _p(pk), _p(st)), "cv_keystore_add")
+        return pk[:n], st[:n]
+
+    def contains(self, pk) -> np.ndarray:
+        """cv_keystore_contains: pk (n,32) u8 -> found u8[n]."""
+        h = self._open()
+        pk = _u8(pk).reshape(-1)
+        if pk.size % 32:
+            raise ValueError("pk must be n x 32 bytes")
+        n = pk.size // 32
+        found = np.zeros(max(n, 1), np.uint8)
+        _check(self._lib.cv_keystore_contains(h, n, _p(pk) if n else None, _p(found)), "cv_keystore_contains")
+        return found[:n]
+
+    def sign(self, pk, arena, off, ln):
+        """cv_keystore_sign: pk (n,32) u8, arena u8, off u64[n], ln u32[n] -> (sig (n,64) u8, status u8[n]: CV_KS_OK, or
+        CV_KS_NO_KEY with a zero signature)."""
+        h = self._open()
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        ln = np.ascontiguousarray(ln, dtype=np.uint32)
+        n = off.shape[0]
+        pk = _arr(pk, np.uint8, n, "pk", 32)
+        if ln.shape[0] != n:
+            raise ValueError("off/len must have n entries")
+        arena = _u8(arena) if arena is not None and np.asarray(arena).size else np.zeros(16, np.uint8)
+        sig, st = np.zeros((max(n, 1), 64), np.uint8), np.zeros(max(n, 1), np.uint8)
+        rc = self._lib.cv_keystore_sign(h, n, _p(pk), _p(arena), arena.size, _p(off), _p(ln), _p(sig), _p(st))
+        if rc == -3 and n and _msg_end(self._lib, off, ln) > arena.size:
+            raise ValueError("message range exceeds the arena")
+        _check(rc, "cv_keystore_sign")
+        return sig[:n], st[:n]
+
+    def sign_transactions(self, arena, leaf_off, leaf_len, tx_leaf_begin, pk, tx_sig_begin):
+        """cv_sign_transactions: leaves as merkle_tx_ids takes them; pk (nsig,32) u8 cut by tx_sig_begin u32[ntx+1] ->
+        (tx_status u8[ntx] CV_ST_*, ids (ntx,32) u8, sig (nsig,64) u8, first_bad u32[ntx])."""
+        h = self._open()
+        ntx, arena, leaf_off, leaf_len, tx_leaf_begin = Engine._merkle_args(arena, leaf_off, leaf_len, tx_leaf_begin)
+        if ntx < 0:
+            raise ValueError("tx_leaf_begin must have ntx + 1 entries")
+        tx_sig_begin = _arr(tx_sig_begin, np.uint32, ntx + 1, "tx_sig_begin")
+        nsig = int(tx_sig_begin[-1])
+        pk = _arr(pk, np.uint8, nsig, "pk", 32)
+        st, ids = np.zeros(max(ntx, 1), np.uint8), np.zeros((max(ntx, 1), 32), np.uint8)
+        sig, fb = np.zeros((max(nsig, 1), 64), np.uint8), np.zeros(max(ntx, 1), np.uint32)
+        rc = self._lib.cv_sign_transactions(self._engine._h, h, ntx, _p(arena), arena.size, _p(leaf_off), _p(leaf_len),
+                                            _p(tx_leaf_begin), nsig, _p(pk), _p(tx_sig_begin), _p(st), _p(ids), _p(sig),
+                                            _p(fb))
+        self._engine._bounded_rc(rc, "cv_sign_transactions", (arena, leaf_off, leaf_len, tx_leaf_begin))
+        return st[:ntx], ids[:ntx], sig[:nsig], fb[:ntx]
+
+    def reserve(self, capacity: int):
+        _check(self._lib.cv_keystore_reserve(self._open(), int(capacity)), "cv_keystore_reserve")
+
+    def stats(self) -> dict:
+        out = np.zeros(len(CV_KS_STATS), np.uint64)
+        _check(self._lib.cv_keystore_stats(self._open(), _p(out), out.size), "cv_keystore_stats")
+        return dict(zip(CV_KS_STATS, map(int, out)))
 
 
 class UniquenessSet:

@@ -69,6 +69,13 @@
  *                                 SignedTransaction.kt:34-38,58-93,134, ServiceHub.kt:46-49: ids, signatures, missing
  *                                 signers, the join of every input against the batch, the duplicate check,
  *                                 topologicalSort and the ordered walk up to its first failure in one call
+ *   cv_keystore_open +        N x  KeyManagementService.freshKey() / keys.contains(pk) / toKeyPair(pk).signWithECDSA(bytes)
+ *   cv_keystore_add / _sign       core/src/main/kotlin/net/corda/core/node/services/Services.kt:206-219 as
+ *                                 PersistentKeyManagementService.kt:40-66 keeps it: a device-resident store of expanded
+ *                                 private keys addressed by public key, every signed record naming its own key
+ *   cv_sign_transactions      N x  the flows' signing loop and the builder's id (CashFlow.kt:39-47,
+ *                                 TwoPartyTradeFlow.kt:227-235, TransactionBuilder.kt:93-98,132-141): ids from the
+ *                                 leaves, then every named key's signature over the id, in one call
  *
  * Conventions
  *   - Return codes: CV_OK (0) or a negative CV_E* code; nothing throws, aborts or longjmps across
@@ -778,6 +785,91 @@ int cv_resolve_batch(cv_ctx *ctx, size_t ntx,
     uint8_t *outcome /* ntx */, uint32_t *first_bad /* ntx, optional */, uint8_t *req_missing /* nreq, optional */,
     uint32_t *bad_input /* ntx */, uint32_t *input_dep /* ninputs */, uint8_t *input_status /* ninputs */,
     uint32_t *order /* ntx */, uint32_t *graph /* CV_RG_WORDS */, uint8_t *ids /* ntx*32, optional */);
+
+/* ---------------------------------------------------------------- the key store (the node's own signing)
+ * KeyManagementService (core/src/main/kotlin/net/corda/core/node/services/Services.kt:189-219) as
+ * PersistentKeyManagementService keeps it (node/src/main/kotlin/net/corda/node/services/keys/
+ * PersistentKeyManagementService.kt:40-66): keys: Map<PublicKey, PrivateKey>, freshKey(), toPrivate(pk) — on one
+ * device of the context, holding the EXPANDED private keys (a | prefix | Abyte, the 96 bytes of a cv_signer record)
+ * addressed by public key, so that a spending node signs a batch in which every record names its own key
+ * (CashFlow.kt:39-47, TwoPartyTradeFlow.kt:227-235,250, TwoPartyDealFlow.kt:254) without a key expansion per
+ * signature and without handing a seed across the ABI per signature.
+ *   - The identity of a key is its 32 encoded bytes.  No single key is deleted (the reference's map never removes
+ *     one); cv_keystore_close overwrites the table before it frees it, and so does the rehash of
+ *     cv_keystore_reserve with the table it replaces.
+ *   - No entry point ever returns a, prefix or a seed, and there is no snapshot: the binding keeps the seeds durable
+ *     (PersistentKeyManagementService's table) and warms a new store with cv_keystore_add.
+ *   - Side channels: as cv_signer — the scalar multiplication selects table entries by secret digits; nothing
+ *     else here branches on, or indexes by, secret data.
+ *   - Calls on one store serialise on a mutex in the store (the reference's ThreadBox); the store has its own stream
+ *     and workspace, so they take no device lock.  A store is closed before its context; cv_keystore_close(NULL) is
+ *     a no-op.
+ *   - Counts: n == 0 (ntx == 0) returns CV_OK and touches nothing; more than 0xfffffffe records: CV_E_TOO_LARGE; so
+ *     is a capacity, or one call, of more than 2^30 keys.  A NULL store, context or required array: CV_E_ARGS.  All
+ *     before any device work.  Outputs as under Conventions. */
+typedef struct cv_keystore cv_keystore;
+#define CV_KS_ADDED 0
+#define CV_KS_PRESENT 1
+#define CV_KS_OK 0
+#define CV_KS_NO_KEY 1
+int cv_keystore_open(cv_ctx *ctx, int device, size_t capacity_keys, cv_keystore **out);
+void cv_keystore_close(cv_keystore *ks);
+/* Room for capacity_keys keys: a rehash on the device into a table of at least twice as many slots; never shrinks. */
+int cv_keystore_reserve(cv_keystore *ks, size_t capacity_keys);
+
+/* N x (entropyToKeyPair / generateKeyPair, CryptoUtilities.kt:117-130) + keys[public] = private
+ * (PersistentKeyManagementService.kt:53-61): seed[i] is expanded on the device, pk_out[i] = its public key, written
+ * for every record, and status[i] = CV_KS_ADDED or CV_KS_PRESENT.  Of several records of one call with the same public
+ * key the FIRST in index order is CV_KS_ADDED; a key already resident is CV_KS_PRESENT and its record is untouched.
+ * The seeds go up through pinned staging that is wiped before the call returns; the device copy is cleared behind the
+ * expansion.  A call that would take the store past its capacity (resident + n, repeats included) returns CV_E_OOM
+ * before any change and any output. */
+int cv_keystore_add(cv_keystore *ks, size_t n, const uint8_t *seed /* n*32 */, uint8_t *pk_out /* n*32 */,
+                    uint8_t *status /* n */);
+
+/* keys.contains(pk) for n keys (PersistentKeyManagementService.kt:51): found[i] = 1 or 0.  Read-only. */
+int cv_keystore_contains(cv_keystore *ks, size_t n, const uint8_t *pk /* n*32 */, uint8_t *found /* n */);
+
+/* N x KeyPair(pk, toPrivate(pk)).signWithECDSA(msg) (Services.kt:206-212, CryptoUtilities.kt:63-73): record i is signed
+ * with ITS OWN key pk[i]; bit for bit cv_ed25519_sign_batch's signature with that key's seed.  A record whose key is
+ * absent (toPrivate's IllegalStateException) gets status CV_KS_NO_KEY and 64 zero bytes; the others are signed
+ * regardless.  A record past msg_arena[msg_arena_bytes), or whose off + len wraps: CV_E_ARGS before any copy. */
+int cv_keystore_sign(cv_keystore *ks, size_t n, const uint8_t *pk /* n*32 */, const uint8_t *msg_arena,
+                     uint64_t msg_arena_bytes, const uint64_t *msg_off, const uint32_t *msg_len,
+                     uint8_t *sig_out /* n*64 */, uint8_t *status /* n */);
+
+/* Diagnostics: out[k] for k < nout (entries past CV_KS_STAT_COUNT are zero). */
+#define CV_KS_STAT_RESIDENT 0
+#define CV_KS_STAT_CAPACITY 1
+#define CV_KS_STAT_SLOTS 2
+#define CV_KS_STAT_PROBE 3        /* longest probe of the table in the last call, in slots */
+#define CV_KS_STAT_COUNT 4
+int cv_keystore_stats(cv_keystore *ks, uint64_t *out, size_t nout);
+
+/* The builder's signing step for a batch (TransactionBuilder.kt:93-98,132-141 under the flows' loops, CashFlow.kt:39-47):
+ * ids from the leaves (as cv_merkle_tx_ids_bounded; they stay on the device as the messages), then transaction t is
+ * signed by keys pk[tx_sig_begin[t] .. tx_sig_begin[t+1]) of the store, sig_out[j] = key j's signature over ids[t].
+ * The keys are walked in order; the first index j (within the transaction) at which something fails settles
+ * tx_status[t] and first_bad[t]:
+ *   CV_ST_NO_KEY          key j is not in the store (IllegalStateException, CashFlow.kt:43 / Services.kt:210)
+ *   CV_ST_ALREADY_SIGNED  key j equals an earlier key of the transaction (TransactionBuilder.kt:94); the scan of the
+ *                         earlier keys is quadratic in ONE transaction's signer count
+ *   CV_ST_EMPTY           no leaves (MerkleTreeException inside the first signWith: only at j = 0, after the two
+ *                         checks above); a transaction with no leaves and no keys is CV_ST_EMPTY with first_bad 0
+ * Otherwise CV_ST_OK with first_bad 0xffffffff (a transaction with leaves and no keys included).  A transaction that
+ * is not CV_ST_OK is abandoned: all of its sig_out are 64 zero bytes; its id is still written (zero for no leaves).
+ * Both range arrays start at 0, are monotone and end at their counts (tx_sig_begin[ntx] == nsig), a leaf past
+ * leaf_arena[leaf_arena_bytes) or wrapping: CV_E_ARGS before any device work; `ks` must belong to `ctx`. */
+#define CV_ST_OK 0
+#define CV_ST_NO_KEY 1
+#define CV_ST_ALREADY_SIGNED 2
+#define CV_ST_EMPTY 3
+int cv_sign_transactions(cv_ctx *ctx, cv_keystore *ks, size_t ntx,
+    const uint8_t *leaf_arena, uint64_t leaf_arena_bytes, const uint64_t *leaf_off, const uint32_t *leaf_len,
+    const uint32_t *tx_leaf_begin /* ntx+1 */,
+    size_t nsig, const uint8_t *pk /* nsig*32 */, const uint32_t *tx_sig_begin /* ntx+1 */,
+    uint8_t *tx_status /* ntx */, uint8_t *ids /* ntx*32 */, uint8_t *sig_out /* nsig*64 */,
+    uint32_t *first_bad /* ntx, optional */);
 
 /* ---------------------------------------------------------------- device-resident API
  * All pointers are device pointers on HIP device `device` (which must be in the context); work is
