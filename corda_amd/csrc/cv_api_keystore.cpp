@@ -1,78 +1,21 @@
 // cv_api_keystore.cpp — the device key store of the C-ABI (include/cordaverify.h): the cv_keystore_* entry points and
-// cv_sign_transactions.  The engine state is cv_host.h's; the range checks and the layout of a call's workspace are
-// cv_batch.h's; the per-lane core is cv_keystore.h.
+// cv_sign_transactions.  The engine state and the resident frame are cv_host.h's; the range checks and the layout of a
+// call's workspace are cv_batch.h's; the per-lane core is cv_keystore.h.
 #include "cv_batch.h"
 
 using namespace cvh;
 
-// The key store.  It lives on one device of its context, with a stream, a workspace, a pinned staging block and a
-// pinned read-back block of its own, so its calls take no device lock: they serialise on the store's mutex.  The
-// table is occ | rec in ONE allocation (cv_keystore.h); growth builds a second one, rehashes on the device, and
-// overwrites the first before it frees it.
-struct cv_keystore {
-    cv_ctx *ctx = nullptr;
-    int ordinal = 0;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    void *tab = nullptr;
-    size_t tab_bytes = 0;
+// The key store: a resident frame (cv_host.h) whose table is occ | rec (cv_keystore.h), overwritten before it is
+// freed, with a pinned staging block for the seeds.
+struct cv_keystore : Resident {
     CvKeyTable T{};
-    size_t capacity = 0, resident = 0;
-    DevBuf ws, dstat;
     PinBuf pin;                              // the seeds on their way up; wiped before cv_keystore_add returns
-    uint32_t *hstat = nullptr;               // pinned: the device counters read back
-    uint64_t last_probe = 0;
 };
 
 namespace {
 
-size_t ks_slots(size_t capacity) {
-    size_t s = 16;
-    while (s < 2 * capacity) s <<= 1;
-    return s;
-}
-
-// a fresh, empty table for `capacity` keys on the current device
-int ks_alloc(size_t capacity, uint64_t seed, hipStream_t s, void **base, size_t *bytes, CvKeyTable *T) {
-    const size_t slots = ks_slots(capacity), total = 4 * slots * (1 + CKS_REC_WORDS);
-    void *p = nullptr;
-    CV_TRY(hipMalloc(&p, total));
-    const hipError_t e = hipMemsetAsync(p, 0, 4 * slots, s);     // occ; a record is written before it is read
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hip_rc(e);
-    }
-    *base = p;
-    *bytes = total;
-    T->occ = static_cast<uint32_t *>(p);
-    T->rec = T->occ + slots;                                     // 4 * slots bytes in: 16-byte aligned (slots >= 16)
-    T->mask = (uint32_t)(slots - 1);
-    T->seed = seed;
-    return CV_OK;
-}
-
-// overwrites a table (every expanded key in it) and frees it
-void ks_wipe_free(void *tab, size_t bytes, hipStream_t s) {
-    if (!tab) return;
-    (void)hipMemsetAsync(tab, 0, bytes, s);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tab);
-}
-
 void wipe(volatile uint8_t *p, size_t n) {
     for (size_t i = 0; i < n; i++) p[i] = 0;
-}
-
-int ks_stat_begin(cv_keystore *ks) {
-    CV_TRY(hipMemsetAsync(ks->dstat.p, 0, 4 * CKS_D_WORDS, ks->stream));
-    return CV_OK;
-}
-// reads the counters back (a synchronisation) and folds them into the store's statistics
-int ks_stat_end(cv_keystore *ks) {
-    CV_TRY(hipMemcpyAsync(ks->hstat, ks->dstat.p, 4 * CKS_D_WORDS, hipMemcpyDeviceToHost, ks->stream));
-    CV_TRY(hipStreamSynchronize(ks->stream));
-    ks->last_probe = ks->hstat[CKS_D_MAXPROBE];
-    return ks->hstat[CKS_D_ERROR] ? CV_E_HIP : CV_OK;            // a probe ran out of slots: never with these sizes
 }
 
 }  // namespace
@@ -80,44 +23,25 @@ int ks_stat_end(cv_keystore *ks) {
 extern "C" {
 
 int cv_keystore_open(cv_ctx *ctx, int device, size_t capacity_keys, cv_keystore **out) {
-    if (out) *out = nullptr;
-    if (!ctx || !out || device < 0 || (size_t)device >= ctx->devs.size()) return CV_E_ARGS;
-    if (capacity_keys > kUniqMaxStates) return CV_E_TOO_LARGE;
+    int rc = Resident::open_check(ctx, device, capacity_keys, out);
+    if (rc != CV_OK) return rc;
     std::unique_ptr<cv_keystore> ks(new (std::nothrow) cv_keystore());
     if (!ks) return CV_E_OOM;
-    ks->ctx = ctx;
-    ks->ordinal = ctx->devs[(size_t)device]->ordinal;
-    ks->capacity = std::max<size_t>(capacity_keys, 1);
     std::random_device rd;
-    const uint64_t seed = key_seed(2) ^ (((uint64_t)rd() << 32) | rd());
-    int rc = hip_rc(hipSetDevice(ks->ordinal));
-    if (rc == CV_OK) rc = hip_rc(hipStreamCreateWithFlags(&ks->stream, hipStreamNonBlocking));
-    if (rc == CV_OK) rc = hip_rc(hipHostMalloc(reinterpret_cast<void **>(&ks->hstat), 4 * CKS_D_WORDS, hipHostMallocDefault));
-    if (rc == CV_OK) rc = hip_rc(ks->dstat.ensure(4 * CKS_D_WORDS, false));
-    if (rc == CV_OK) rc = ks_alloc(ks->capacity, seed, ks->stream, &ks->tab, &ks->tab_bytes, &ks->T);
-    if (rc == CV_OK) rc = hip_rc(hipStreamSynchronize(ks->stream));
+    const uint64_t seed = key_seed(2) ^ rand64(rd);
+    rc = ks->open(ctx, device, capacity_keys, CKS_SLOT_BYTES, CKS_D_WORDS, true);   // tables overwritten before freed
     if (rc != CV_OK) {
         cv_keystore_close(ks.release());
         return rc;
     }
+    ks->T = cks_carve(ks->tab, ks->slots, seed);
     *out = ks.release();
     return CV_OK;
 }
 
 void cv_keystore_close(cv_keystore *ks) {
     if (!ks) return;
-    (void)hipSetDevice(ks->ordinal);
-    if (ks->stream) {
-        (void)hipStreamSynchronize(ks->stream);
-        ks_wipe_free(ks->tab, ks->tab_bytes, ks->stream);
-    } else if (ks->tab) {
-        (void)hipFree(ks->tab);                                  // open failed before anything was put
-    }
-    ks->ws.release();
-    ks->dstat.release();
-    ks->pin.release();
-    if (ks->hstat) (void)hipHostFree(ks->hstat);
-    if (ks->stream) (void)hipStreamDestroy(ks->stream);
+    ks->close([ks] { ks->pin.release(); });
     delete ks;
 }
 
@@ -125,37 +49,23 @@ int cv_keystore_reserve(cv_keystore *ks, size_t capacity_keys) {
     if (!ks) return CV_E_ARGS;
     if (capacity_keys > kUniqMaxStates) return CV_E_TOO_LARGE;
     std::lock_guard<std::mutex> g(ks->mu);
-    if (capacity_keys <= ks->capacity) return CV_OK;             // never shrinks
-    CV_TRY(hipSetDevice(ks->ordinal));
-    if (ks_slots(capacity_keys) == (size_t)ks->T.mask + 1) {     // the slots already hold it
-        ks->capacity = capacity_keys;
-        return CV_OK;
-    }
-    void *base = nullptr;
-    size_t bytes = 0;
     CvKeyTable to{};
-    int rc = ks_alloc(capacity_keys, ks->T.seed, ks->stream, &base, &bytes, &to);
-    if (rc != CV_OK) return rc;
-    rc = ks_stat_begin(ks);
-    if (rc == CV_OK) rc = hip_rc(cvk_ks_rehash(&ks->T, &to, ks->dstat.as<uint32_t>(), ks->stream));
-    const int rc2 = ks_stat_end(ks);                             // synchronises, also after a failed launch
-    if (rc == CV_OK) rc = rc2;
-    if (rc != CV_OK) {
-        ks_wipe_free(base, bytes, ks->stream);                   // the old table is untouched
-        return rc;
-    }
-    ks_wipe_free(ks->tab, ks->tab_bytes, ks->stream);
-    ks->tab = base;
-    ks->tab_bytes = bytes;
-    ks->T = to;
-    ks->capacity = capacity_keys;
-    return CV_OK;
+    bool rehashed = false;
+    const int rc = ks->grow(
+        capacity_keys,
+        [&](void *base, size_t slots) {
+            to = cks_carve(base, slots, ks->T.seed);
+            return cvk_ks_rehash(&ks->T, &to, ks->dstat.as<uint32_t>(), ks->stream);
+        },
+        [ks] { return ks->stat_end(); }, &rehashed);
+    if (rehashed) ks->T = to;
+    return rc;
 }
 
 int cv_keystore_stats(cv_keystore *ks, uint64_t *out, size_t nout) {
     if (!ks || (nout && !out)) return CV_E_ARGS;
     std::lock_guard<std::mutex> g(ks->mu);
-    const uint64_t v[CV_KS_STAT_COUNT] = {ks->resident, ks->capacity, (uint64_t)ks->T.mask + 1, ks->last_probe};
+    const uint64_t v[CV_KS_STAT_COUNT] = {ks->resident, ks->capacity, (uint64_t)ks->slots, ks->last_probe};
     for (size_t k = 0; k < nout; k++) out[k] = k < CV_KS_STAT_COUNT ? v[k] : 0;
     return CV_OK;
 }
@@ -185,7 +95,7 @@ int cv_keystore_add(cv_keystore *ks, size_t n, const uint8_t *seed, uint8_t *pk_
     });
     std::memcpy(pin, seed, 32 * n);
     CV_TRY(hipMemcpyAsync(base + o_seed, pin, 32 * n, hipMemcpyHostToDevice, s));
-    int rc = ks_stat_begin(ks);
+    int rc = ks->stat_begin();
     if (rc != CV_OK) return rc;
     const CvDedupe D = cvd_args(n, base + o_pk, nullptr, nullptr, nullptr, base + o_dd, key_seed(3) | 1, L);
     hipError_t e = cvk_ks_add(&ks->T, &D, base + o_seed, at<uint32_t>(base, o_rec), base + o_st, ks->dstat.as<uint32_t>(), s);
@@ -193,9 +103,9 @@ int cv_keystore_add(cv_keystore *ks, size_t n, const uint8_t *seed, uint8_t *pk_
     const hipError_t e2 = hipMemsetAsync(base + o_seed, 0, o_pk - o_seed, s);
     if (e == hipSuccess) e = e2;
     CV_TRY(e);
-    rc = ks_stat_end(ks);
+    rc = ks->stat_end();
     if (rc != CV_OK) return rc;
-    ks->resident += ks->hstat[CKS_D_ADDED];
+    ks->resident += ks->hstat[CKS_D_ADDED];                      // the store's extra
     CV_TRY(hipMemcpyAsync(pk_out, base + o_pk, 32 * n, hipMemcpyDeviceToHost, s));
     CV_TRY(hipMemcpyAsync(status, base + o_st, n, hipMemcpyDeviceToHost, s));
     CV_TRY(hipStreamSynchronize(s));
@@ -217,10 +127,10 @@ int cv_keystore_contains(cv_keystore *ks, size_t n, const uint8_t *pk, uint8_t *
     hipStream_t s = ks->stream;
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });   // the pageable copies read the caller's arrays
     CV_TRY(hipMemcpyAsync(base + o_pk, pk, 32 * n, hipMemcpyHostToDevice, s));
-    int rc = ks_stat_begin(ks);
+    int rc = ks->stat_begin();
     if (rc != CV_OK) return rc;
     CV_TRY(cvk_ks_lookup(&ks->T, (uint32_t)n, at<uint32_t>(base, o_pk), nullptr, base + o_f, 1, ks->dstat.as<uint32_t>(), s));
-    rc = ks_stat_end(ks);
+    rc = ks->stat_end();
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(found, base + o_f, n, hipMemcpyDeviceToHost, s));
     CV_TRY(hipStreamSynchronize(s));
@@ -252,14 +162,14 @@ int cv_keystore_sign(cv_keystore *ks, size_t n, const uint8_t *pk, const uint8_t
     CV_TRY(hipMemcpyAsync(base + o_off, msg_off, 8 * n, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(base + o_len, msg_len, 4 * n, hipMemcpyHostToDevice, s));
     if (hi > lo) CV_TRY(hipMemcpyAsync(base + o_ar, msg_arena + lo, hi - lo, hipMemcpyHostToDevice, s));
-    int rc = ks_stat_begin(ks);
+    int rc = ks->stat_begin();
     if (rc != CV_OK) return rc;
     CV_TRY(cvk_ks_lookup(&ks->T, (uint32_t)n, at<uint32_t>(base, o_pk), at<uint32_t>(base, o_slot), base + o_st, CV_KS_OK,
                          ks->dstat.as<uint32_t>(), s));
     // the offsets are the caller's: the arena pointer is moved back by the part that was not copied
     CV_TRY(cvk_ks_sign(&ks->T, (uint32_t)n, at<uint32_t>(base, o_slot), base + o_ar - lo, at<uint64_t>(base, o_off),
                        at<uint32_t>(base, o_len), base + o_sig, s));
-    rc = ks_stat_end(ks);
+    rc = ks->stat_end();
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(sig_out, base + o_sig, 64 * n, hipMemcpyDeviceToHost, s));
     CV_TRY(hipMemcpyAsync(status, base + o_st, n, hipMemcpyDeviceToHost, s));
@@ -306,7 +216,7 @@ int cv_sign_transactions(cv_ctx *ctx, cv_keystore *ks, size_t ntx, const uint8_t
     CV_TRY(hipMemcpyAsync(base + i_txb, tx_leaf_begin, 4 * (T + 1), hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(base + i_tsb, tx_sig_begin, 4 * (T + 1), hipMemcpyHostToDevice, s));
     if (N) CV_TRY(hipMemcpyAsync(base + i_pk, pk, 32 * N, hipMemcpyHostToDevice, s));
-    int rc = ks_stat_begin(ks);
+    int rc = ks->stat_begin();
     if (rc != CV_OK) return rc;
     // the ids: leaf hashes, then the trees; they stay where the signing kernel reads them as its messages
     CV_TRY(cvk_merkle((uint32_t)T, (uint32_t)L, 0, base + i_arena - lo, at<uint64_t>(base, i_loff), at<uint32_t>(base, i_llen),
@@ -319,7 +229,7 @@ int cv_sign_transactions(cv_ctx *ctx, cv_keystore *ks, size_t ntx, const uint8_t
     X.dstat = ks->dstat.as<uint32_t>();
     CV_TRY(cvk_ks_tx_gate(&ks->T, &X, s));
     CV_TRY(cvk_ks_sign(&ks->T, (uint32_t)N, X.slot, base + o_ids, X.off, X.len, base + o_sig, s));
-    rc = ks_stat_end(ks);
+    rc = ks->stat_end();
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(tx_status, base + o_st, T, hipMemcpyDeviceToHost, s));
     CV_TRY(hipMemcpyAsync(ids, base + o_ids, 32 * T, hipMemcpyDeviceToHost, s));

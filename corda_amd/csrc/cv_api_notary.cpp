@@ -74,7 +74,7 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
     CV_TRY(hipSetDevice(u->ordinal));
     // inputs (one upload) | workspace | outputs (one read-back)
     Layout lay;
-    const size_t R = nreq, W = (N + 63) / 64, bs = (size_t)uniq_bmask(S) + 1;
+    const size_t R = nreq, W = (N + 63) / 64, bs = uniq_bslots(S);
     const size_t i_arena = lay.take(hi - lo), i_loff = lay.take(8 * L), i_llen = lay.take(4 * L);
     const size_t i_txb = lay.take(4 * (T + 1)), i_claim = lay.take(32 * T), i_cal = lay.take(4 * T), i_tpre = lay.take(T);
     const size_t i_sbeg = lay.take(4 * (T + 1)), i_sleaf = lay.take(4 * S), i_pk = lay.take(32 * N);
@@ -145,7 +145,7 @@ int cv_notarise_batch(cv_ctx *ctx, cv_uniq *u, const cv_signer *sg, int validati
     uint8_t *base = u->nws.as<uint8_t>();
     hipStream_t s = u->stream;
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
-    int rc = uniq_stat_begin(u);
+    int rc = u->stat_begin();
     if (rc != CV_OK) return rc;
     CV_TRY(hipMemcpyAsync(base, h, in_bytes, hipMemcpyHostToDevice, s));
     // the key dedupe ahead of the Merkle kernels; its count and keys come back through the outputs' pinned block

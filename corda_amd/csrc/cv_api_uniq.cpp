@@ -5,69 +5,16 @@
 
 using namespace cvh;
 
-extern "C" {
-
 // ---------------------------------------------------------------- uniqueness set (the notary's commit step)
 
 #define CV_UNIQ_SNAP_BLOCK 256u   // slots per block of the snapshot's kernels (cv_k_uniq.hip: CV_BLOCK)
 
-static size_t uniq_slots(size_t capacity) {
-    size_t s = 16;
-    while (s < 2 * capacity) s <<= 1;
-    return s;
-}
-
-static void uniq_carve(void *base, size_t slots, uint64_t seed, CvUniqTable *T) {
-    uint32_t *p = static_cast<uint32_t *>(base);
-    T->occ = p;
-    T->key = p + slots;
-    T->id = p + 9 * slots;
-    T->index = p + 17 * slots;
-    T->caller = p + 18 * slots;
-    T->mask = (uint32_t)(slots - 1);
-    T->seed = seed;
-}
-
-// a fresh, empty table for `capacity` states on the current device
-static int uniq_alloc(size_t capacity, uint64_t seed, hipStream_t s, void **base, CvUniqTable *T) {
-    const size_t slots = uniq_slots(capacity);
-    void *p = nullptr;
-    CV_TRY(hipMalloc(&p, 76 * slots));
-    const hipError_t e = hipMemsetAsync(p, 0, 4 * slots, s);     // occ; the other arrays are written before they are read
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hip_rc(e);
-    }
-    *base = p;
-    uniq_carve(p, slots, seed, T);
-    return CV_OK;
-}
-
-}  // extern "C"
-
-// counters zeroed before a call's kernels / read back and folded into the set's statistics after them
 namespace cvh {
-int uniq_stat_begin(cv_uniq *u) {
-    CV_TRY(hipMemsetAsync(u->dstat.p, 0, 4 * CVU_D_WORDS, u->stream));
-    return CV_OK;
-}
-static int uniq_stat_read(cv_uniq *u) {
-    CV_TRY(hipMemcpyAsync(u->hstat, u->dstat.p, 4 * CVU_D_WORDS, hipMemcpyDeviceToHost, u->stream));
-    CV_TRY(hipStreamSynchronize(u->stream));
-    return CV_OK;
-}
+// the frame's stat_end, and the set's extra: its wraps
 int uniq_stat_end(cv_uniq *u) {
-    const int rc = uniq_stat_read(u);
-    if (rc != CV_OK) return rc;
-    u->last_probe = u->hstat[CVU_D_MAXPROBE];
+    const int rc = u->stat_end();
     u->wraps += u->hstat[CVU_D_WRAPS];
-    return u->hstat[CVU_D_ERROR] ? CV_E_HIP : CV_OK;            // a probe ran out of slots: never with the sizes above
-}
-
-uint32_t uniq_bmask(size_t nstates) {
-    size_t s = 16;
-    while (s < 2 * nstates) s <<= 1;
-    return (uint32_t)(s - 1);
+    return rc;
 }
 
 // The decision of one batch on the set's stream: front, then rounds while the device says a request is undecided (one
@@ -96,43 +43,30 @@ int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, 
 extern "C" {
 
 int cv_uniq_open(cv_ctx *ctx, int device, size_t capacity_states, cv_uniq **out) {
-    if (out) *out = nullptr;
-    if (!ctx || !out || device < 0 || (size_t)device >= ctx->devs.size()) return CV_E_ARGS;
-    if (capacity_states > kUniqMaxStates) return CV_E_TOO_LARGE;
+    int rc = Resident::open_check(ctx, device, capacity_states, out);
+    if (rc != CV_OK) return rc;
     std::unique_ptr<cv_uniq> u(new (std::nothrow) cv_uniq());
     if (!u) return CV_E_OOM;
-    u->ctx = ctx;
-    u->ordinal = ctx->devs[(size_t)device]->ordinal;
-    u->capacity = std::max<size_t>(capacity_states, 1);
     std::random_device rd;
-    const uint64_t seed = key_seed(0) ^ (((uint64_t)rd() << 32) | rd());
-    u->epoch = (((uint64_t)rd() << 32) | rd()) | 1;              // a cursor of another set does not continue on this one
-    int rc = hip_rc(hipSetDevice(u->ordinal));
-    if (rc == CV_OK) rc = hip_rc(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
-    if (rc == CV_OK) rc = hip_rc(hipHostMalloc(reinterpret_cast<void **>(&u->hstat), 4 * CVU_D_WORDS, hipHostMallocDefault));
-    if (rc == CV_OK) rc = hip_rc(u->dstat.ensure(4 * CVU_D_WORDS, false));
-    if (rc == CV_OK) rc = uniq_alloc(u->capacity, seed, u->stream, &u->tab, &u->T);
-    if (rc == CV_OK) rc = hip_rc(hipStreamSynchronize(u->stream));
+    const uint64_t seed = key_seed(0) ^ rand64(rd);
+    u->epoch = rand64(rd) | 1;                                   // a cursor of another set does not continue on this one
+    rc = u->open(ctx, device, capacity_states, CVU_SLOT_BYTES, CVU_D_WORDS, false);   // freed, not overwritten
     if (rc != CV_OK) {
         cv_uniq_close(u.release());
         return rc;
     }
+    u->T = cvu_carve(u->tab, u->slots, seed);
     *out = u.release();
     return CV_OK;
 }
 
 void cv_uniq_close(cv_uniq *u) {
     if (!u) return;
-    (void)hipSetDevice(u->ordinal);
-    if (u->stream) (void)hipStreamSynchronize(u->stream);
-    if (u->tab) (void)hipFree(u->tab);
-    u->ws.release();
-    u->nws.release();
-    u->nin.release();
-    u->nout.release();
-    u->dstat.release();
-    if (u->hstat) (void)hipHostFree(u->hstat);
-    if (u->stream) (void)hipStreamDestroy(u->stream);
+    u->close([u] {
+        u->nws.release();
+        u->nin.release();
+        u->nout.release();
+    });
     delete u;
 }
 
@@ -140,30 +74,20 @@ int cv_uniq_reserve(cv_uniq *u, size_t capacity_states) {
     if (!u) return CV_E_ARGS;
     if (capacity_states > kUniqMaxStates) return CV_E_TOO_LARGE;
     std::lock_guard<std::mutex> g(u->mu);
-    if (capacity_states <= u->capacity) return CV_OK;            // never shrinks
-    CV_TRY(hipSetDevice(u->ordinal));
-    if (uniq_slots(capacity_states) == (size_t)u->T.mask + 1) {  // the slots already hold it
-        u->capacity = capacity_states;
-        return CV_OK;
-    }
-    void *base = nullptr;
     CvUniqTable to{};
-    int rc = uniq_alloc(capacity_states, u->T.seed, u->stream, &base, &to);
-    if (rc != CV_OK) return rc;
-    rc = uniq_stat_begin(u);
-    if (rc == CV_OK) rc = hip_rc(cvk_uniq_rehash(&u->T, &to, u->dstat.as<uint32_t>(), u->stream));
-    const int rc2 = uniq_stat_end(u);                            // synchronises, also after a failed launch
-    if (rc == CV_OK) rc = rc2;
-    if (rc != CV_OK) {
-        (void)hipFree(base);                                     // the old table is untouched
-        return rc;
+    bool rehashed = false;
+    const int rc = u->grow(
+        capacity_states,
+        [&](void *base, size_t slots) {
+            to = cvu_carve(base, slots, u->T.seed);
+            return cvk_uniq_rehash(&u->T, &to, u->dstat.as<uint32_t>(), u->stream);
+        },
+        [u] { return uniq_stat_end(u); }, &rehashed);
+    if (rehashed) {
+        u->T = to;
+        u->touch();                                              // the slots moved
     }
-    (void)hipFree(u->tab);
-    u->tab = base;
-    u->T = to;
-    u->capacity = capacity_states;
-    u->touch();                                                  // the slots moved
-    return CV_OK;
+    return rc;
 }
 
 int cv_uniq_set_max_rounds(cv_uniq *u, int rounds) {
@@ -176,7 +100,7 @@ int cv_uniq_set_max_rounds(cv_uniq *u, int rounds) {
 int cv_uniq_stats(cv_uniq *u, uint64_t *out, size_t nout) {
     if (!u || (nout && !out)) return CV_E_ARGS;
     std::lock_guard<std::mutex> g(u->mu);
-    const uint64_t v[CV_UNIQ_STAT_COUNT] = {u->resident, u->capacity, (uint64_t)u->T.mask + 1, u->last_rounds,
+    const uint64_t v[CV_UNIQ_STAT_COUNT] = {u->resident, u->capacity, (uint64_t)u->slots, u->last_rounds,
                                             u->last_tail, u->last_probe, u->wraps};
     for (size_t k = 0; k < nout; k++) out[k] = k < CV_UNIQ_STAT_COUNT ? v[k] : 0;
     return CV_OK;
@@ -198,7 +122,7 @@ int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const
     std::lock_guard<std::mutex> g(u->mu);
     if (u->resident + S > u->capacity) return CV_E_OOM;          // before any change and any output
     CV_TRY(hipSetDevice(u->ordinal));
-    const size_t T = ntx, bs = (size_t)uniq_bmask(S) + 1;
+    const size_t T = ntx, bs = uniq_bslots(S);
     // inputs | workspace | outputs (tx_status | state_conflict | consumed id, index, caller: one copy-back region)
     Layout lay;
     const size_t o_key = lay.take(32 * S), o_beg = lay.take(4 * (T + 1)), o_id = lay.take(32 * T), o_cal = lay.take(4 * T);
@@ -216,7 +140,7 @@ int cv_uniq_commit_batch(cv_uniq *u, size_t ntx, const uint8_t *state_key, const
     CV_TRY(hipMemcpyAsync(base + o_cal, caller, 4 * T, hipMemcpyHostToDevice, s));
     if (tx_enable) CV_TRY(hipMemcpyAsync(base + o_en, tx_enable, T, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemsetAsync(base + o_cid, 0, lay.top - o_cid, s));   // records of states without a conflict: zero
-    int rc = uniq_stat_begin(u);
+    int rc = u->stat_begin();
     if (rc != CV_OK) return rc;
     CvUniqBatch B{};
     B.ntx = (uint32_t)T;
@@ -275,7 +199,7 @@ int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key, uint8_t *foun
     auto drain = on_exit([s] { (void)hipStreamSynchronize(s); });
     CV_TRY(hipMemcpyAsync(base + o_key, state_key, 32 * n, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemsetAsync(base + o_cid, 0, lay.top - o_cid, s));   // absent keys: zero records
-    int rc = uniq_stat_begin(u);
+    int rc = u->stat_begin();
     if (rc != CV_OK) return rc;
     CV_TRY(cvk_uniq_lookup(&u->T, (uint32_t)n, at<uint32_t>(base, o_key), base + o_f, at<uint32_t>(base, o_cid),
                            at<uint32_t>(base, o_cix), at<uint32_t>(base, o_cc), u->dstat.as<uint32_t>(), s));
@@ -292,7 +216,7 @@ int cv_uniq_lookup(cv_uniq *u, size_t n, const uint8_t *state_key, uint8_t *foun
 // first (a key repeated in the call, or resident in T: CV_E_ARGS, T unchanged), then the inserts.  Synchronises.
 static int uniq_load_into(cv_uniq *u, const CvUniqTable &T, size_t n, const uint8_t *state_key, const uint8_t *consumed_id,
                           const uint32_t *consumed_index, const uint32_t *consumed_caller) {
-    const size_t bs = (size_t)uniq_bmask(n) + 1;
+    const size_t bs = uniq_bslots(n);
     Layout lay;
     const size_t o_key = lay.take(32 * n), o_id = lay.take(32 * n), o_ix = lay.take(4 * n), o_cal = lay.take(4 * n);
     const size_t o_bt = lay.take(4 * bs), o_rep = lay.take(4 * n), o_res = lay.take(4 * n);
@@ -304,7 +228,7 @@ static int uniq_load_into(cv_uniq *u, const CvUniqTable &T, size_t n, const uint
     CV_TRY(hipMemcpyAsync(base + o_id, consumed_id, 32 * n, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(base + o_ix, consumed_index, 4 * n, hipMemcpyHostToDevice, s));
     CV_TRY(hipMemcpyAsync(base + o_cal, consumed_caller, 4 * n, hipMemcpyHostToDevice, s));
-    int rc = uniq_stat_begin(u);
+    int rc = u->stat_begin();
     if (rc != CV_OK) return rc;
     CvUniqBatch B{};
     B.nstates = (uint32_t)n;
@@ -319,7 +243,7 @@ static int uniq_load_into(cv_uniq *u, const CvUniqTable &T, size_t n, const uint
     B.dstat = u->dstat.as<uint32_t>();
     // the check first (a key repeated in the call, or resident): the table changes only after it passed
     CV_TRY(cvk_uniq_load(&T, &B, 0, s));
-    rc = uniq_stat_read(u);
+    rc = u->stat_read();
     if (rc != CV_OK) return rc;
     if (u->hstat[CVU_D_ERROR]) {
         drain.armed = false;
@@ -439,21 +363,19 @@ int cv_uniq_install(cv_uniq *u, size_t n, const uint8_t *state_key, const uint8_
     // a fresh table beside the old one, as cv_uniq_reserve builds it: the old one serves until the new one is whole
     const size_t capacity = std::max(u->capacity, n);
     std::random_device rd;
-    const uint64_t seed = key_seed(0) ^ (((uint64_t)rd() << 32) | rd());
     void *base = nullptr;
-    CvUniqTable to{};
-    int rc = uniq_alloc(capacity, seed, u->stream, &base, &to);
+    size_t slots = 0;
+    int rc = u->alloc(capacity, &base, &slots);
     if (rc != CV_OK) return rc;
+    const CvUniqTable to = cvu_carve(base, slots, key_seed(0) ^ rand64(rd));
     rc = uniq_load_into(u, to, n, state_key, consumed_id, consumed_index, consumed_caller);
     if (rc != CV_OK) {
         (void)hipStreamSynchronize(u->stream);
-        (void)hipFree(base);                                     // the old table is untouched
+        u->drop(base, slots);                                    // the old table is untouched
         return rc;
     }
-    (void)hipFree(u->tab);
-    u->tab = base;
+    u->adopt(base, slots, capacity);
     u->T = to;
-    u->capacity = capacity;
     u->resident = n;
     u->touch();
     return CV_OK;

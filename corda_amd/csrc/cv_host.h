@@ -496,22 +496,153 @@ struct cv_signer {
     uint8_t pk[32] = {};
 };
 
-// The uniqueness set (cv_api_uniq.cpp).  It lives on one device of its context, with a stream, a workspace and a
-// pinned read-back block of its own, so its calls take no device lock: they serialise on the set's mutex (the
-// reference's ThreadBox).  The table is five arrays in ONE allocation (occ | key | id | index | caller, cv_uniq.h);
-// growth builds a second one, rehashes on the device and frees the first.
-struct cv_uniq {
+namespace cvh {
+
+constexpr size_t kUniqMaxStates = (size_t)1 << 30;   // a table's slot count stays within 2^31
+
+inline uint64_t rand64(std::random_device &rd) { return ((uint64_t)rd() << 32) | rd(); }
+
+// The host frame of a device-resident table (cv_table.h): what the uniqueness set and the key store share.  It lives
+// on one device of its context, with a stream, a workspace and a pinned read-back block of its own, so its calls take
+// no device lock: they serialise on the mutex.  The table is ONE allocation of slots * slot_bytes with occ first, the
+// slot count cv_table_slots(capacity, 16); its owner carves it (cvu_carve, cks_carve) and keeps the seed.  Words
+// CVT_D_ERROR and CVT_D_MAXPROBE of the stat_words device counters are folded here, the rest by the owner.
+struct Resident {
     cv_ctx *ctx = nullptr;
     int ordinal = 0;
     std::mutex mu;
     hipStream_t stream = nullptr;
     void *tab = nullptr;
-    CvUniqTable T{};
+    size_t slots = 0, slot_bytes = 0;
     size_t capacity = 0, resident = 0;
-    cvh::DevBuf ws, dstat;
+    DevBuf ws, dstat;
     uint32_t *hstat = nullptr;               // pinned: the device counters read back
+    size_t stat_words = 0;
+    uint64_t last_probe = 0;
+    bool wipe = false;                       // overwrite a table before freeing it (the store: it holds private keys)
+
+    // the open entry points' checks, in their order
+    template <class H> static int open_check(cv_ctx *c, int device, size_t cap, H **out) {
+        if (out) *out = nullptr;
+        if (!c || !out || device < 0 || (size_t)device >= c->devs.size()) return CV_E_ARGS;
+        return cap > kUniqMaxStates ? CV_E_TOO_LARGE : CV_OK;
+    }
+    // a fresh, empty table for `cap` entries on the current device: occ zeroed on the stream, the rest is written
+    // before it is read
+    int alloc(size_t cap, void **base, size_t *nslots) {
+        const size_t n = (size_t)cv_table_slots(cap, 16);
+        void *p = nullptr;
+        CV_TRY(hipMalloc(&p, slot_bytes * n));
+        const hipError_t e = hipMemsetAsync(p, 0, 4 * n, stream);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return hip_rc(e);
+        }
+        *base = p;
+        *nslots = n;
+        return CV_OK;
+    }
+    void drop(void *base, size_t nslots) {
+        if (!base) return;
+        if (wipe && stream) {
+            (void)hipMemsetAsync(base, 0, slot_bytes * nslots, stream);
+            (void)hipStreamSynchronize(stream);
+        }
+        (void)hipFree(base);
+    }
+    void adopt(void *base, size_t nslots, size_t cap) {
+        drop(tab, slots);
+        tab = base;
+        slots = nslots;
+        capacity = cap;
+    }
+    // after open_check; a failure leaves what was made so far to close()
+    int open(cv_ctx *c, int device, size_t cap, size_t sbytes, size_t swords, bool wipe_tables) {
+        ctx = c;
+        ordinal = c->devs[(size_t)device]->ordinal;
+        capacity = std::max<size_t>(cap, 1);
+        slot_bytes = sbytes;
+        stat_words = swords;
+        wipe = wipe_tables;
+        CV_TRY(hipSetDevice(ordinal));
+        CV_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        CV_TRY(hipHostMalloc(reinterpret_cast<void **>(&hstat), 4 * stat_words, hipHostMallocDefault));
+        CV_TRY(dstat.ensure(4 * stat_words, false));
+        const int rc = alloc(capacity, &tab, &slots);
+        if (rc != CV_OK) return rc;
+        CV_TRY(hipStreamSynchronize(stream));
+        return CV_OK;
+    }
+    // release_own: the owner's buffers, released where they always were: behind the table and the workspace, ahead
+    // of the counters and the stream
+    template <class Own> void close(Own release_own) {
+        (void)hipSetDevice(ordinal);
+        if (stream) (void)hipStreamSynchronize(stream);
+        drop(tab, slots);
+        tab = nullptr;
+        ws.release();
+        release_own();
+        dstat.release();
+        if (hstat) (void)hipHostFree(hstat);
+        if (stream) (void)hipStreamDestroy(stream);
+        hstat = nullptr, stream = nullptr;
+    }
+    // counters zeroed before a call's kernels / read back (a synchronisation) and folded after them
+    int stat_begin() {
+        CV_TRY(hipMemsetAsync(dstat.p, 0, 4 * stat_words, stream));
+        return CV_OK;
+    }
+    int stat_read() {
+        hipError_t e = hipMemcpyAsync(hstat, dstat.p, 4 * stat_words, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) std::memset(hstat, 0, 4 * stat_words);   // nothing for the owner's folds to add
+        return hip_rc(e);
+    }
+    int stat_end() {
+        const int rc = stat_read();
+        if (rc != CV_OK) return rc;
+        last_probe = hstat[CVT_D_MAXPROBE];
+        return hstat[CVT_D_ERROR] ? CV_E_HIP : CV_OK;         // a probe ran out of slots: never with these sizes
+    }
+    // Growth to `cap` entries (never shrinks), the caller holding mu: a fresh table, rehash(base, slots) — the
+    // owner's launcher from the old table into the new one — between stat_begin and end(), the owner's stat end (the
+    // frame's, or one that folds more); the swap on success, and on failure the new table dropped and the old one
+    // untouched.  *rehashed says whether tab is a new table now (false: nothing to do, or the slots already held it).
+    template <class Rehash, class End> int grow(size_t cap, Rehash rehash, End end, bool *rehashed) {
+        *rehashed = false;
+        if (cap <= capacity) return CV_OK;
+        CV_TRY(hipSetDevice(ordinal));
+        if ((size_t)cv_table_slots(cap, 16) == slots) {          // the slots already hold it
+            capacity = cap;
+            return CV_OK;
+        }
+        void *base = nullptr;
+        size_t nslots = 0;
+        int rc = alloc(cap, &base, &nslots);
+        if (rc != CV_OK) return rc;
+        rc = stat_begin();
+        if (rc == CV_OK) rc = hip_rc(rehash(base, nslots));
+        const int rc2 = end();                                   // synchronises, also after a failed launch
+        if (rc == CV_OK) rc = rc2;
+        if (rc != CV_OK) {
+            drop(base, nslots);
+            return rc;
+        }
+        adopt(base, nslots, cap);
+        *rehashed = true;
+        return CV_OK;
+    }
+};
+
+}  // namespace cvh
+
+// The uniqueness set (cv_api_uniq.cpp): a resident frame (its mutex is the reference's ThreadBox) whose table is five
+// arrays (occ | key | id | index | caller, cv_uniq.h); growth builds a second one, rehashes on the device and frees
+// the first.
+struct cv_uniq : cvh::Resident {
+    CvUniqTable T{};
     int max_rounds = 8;
-    uint64_t last_rounds = 0, last_tail = 0, last_probe = 0, wraps = 0;
+    uint64_t last_rounds = 0, last_tail = 0, wraps = 0;
     // advanced by every call that may change the table's contents or layout (commit, load, install, clear, a reserve
     // that rehashes); a snapshot cursor carries the value of the call that started its pass.  Never 0.
     uint64_t epoch = 1;
@@ -527,13 +658,10 @@ struct cv_uniq {
 
 namespace cvh {
 
-constexpr size_t kUniqMaxStates = (size_t)1 << 30;   // a table's slot count stays within 2^31
-
-// cv_api_uniq.cpp, shared with cv_api_notary.cpp: the counters zeroed before a call's kernels / read back (a
-// synchronisation) and folded into the set's statistics after them, the batch table's mask, the decision itself
-int uniq_stat_begin(cv_uniq *u);
+// cv_api_uniq.cpp, shared with cv_api_notary.cpp: the frame's stat_end with the set's wraps folded, the slots of a
+// batch's table of state indices, the decision itself
 int uniq_stat_end(cv_uniq *u);
-uint32_t uniq_bmask(size_t nstates);
+inline size_t uniq_bslots(size_t nstates) { return (size_t)cv_table_slots(nstates, 16); }
 int uniq_decide(cv_uniq *u, const CvUniqBatch &B, uint32_t *cur, uint32_t *nxt, uint64_t *rounds);
 
 // cv_api.cpp: one verify launch group of n signatures (device pointers, as cv_ed25519_verify_device) on stream s of

@@ -6,9 +6,8 @@
 // atomics reduce to plain operations there).
 //
 // ONE dedupe, a kernel per step, no lane reading what another lane of its kernel writes except through an atomic:
-//   insert  per signature i: atomicCAS(slot, NONE, i) into a call-local open-addressing table of signature INDICES: a
-//           power-of-two slot count of at least 2 n, linear probing, the slot from cvu_hash's seeded mix of all eight
-//           key words (a key is 32 bytes a submitter chooses: no key bits choose a slot directly).  A loser compares
+//   insert  per signature i: atomicCAS(slot, NONE, i) into a call-local table of signature INDICES (a table of
+//           cv_table.h: probing, sizing and hashing are described there; a floor of 2 slots).  A loser compares
 //           pk[occupant] with pk[i] — both in the immutable input — and probes on, or, on equality, does
 //           atomicMin(slot, i): the slot ends at the key's FIRST occurrence, whichever lane won.  Two things keep
 //           the lanes of a batch of few keys off each other's atomics (all of one address run one after another): a
@@ -28,9 +27,10 @@
 // ran first, but the slot's final value does not: every lane that carries the key either claims the slot or lowers it
 // with atomicMin, so it ends at the smallest index with that key.  first[], the flags, their prefix sums (index order)
 // and so keys, key_index and nkeys follow from that alone.
-// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE LOOP IS BOUNDED by the slot count and clears
-// stat[CVD_STAT_OK] when it runs out; emit then reports nkeys = CVD_NONE (no batch has that many keys) and a host
-// that reads the count back returns CV_E_HIP.  The slot count rules it out.
+// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE IS BOUNDED: each is cv_walk (cv_table.h), which
+// looks at no more than the slot count, and clears stat[CVD_STAT_OK] when it runs out; emit then reports
+// nkeys = CVD_NONE (no batch has that many keys) and a host that reads the count back returns CV_E_HIP.  The slot
+// count rules it out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,59 +56,37 @@ struct CvDedupe {
     uint32_t *keys, *key_index, *nkeys;
 };
 
-// an atomic read of a slot other lanes of the kernel change (relaxed: any value the slot has held will do)
-CV_HD uint32_t cvd_atomic_load(const uint32_t *p) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return *p;
-#endif
-}
-
 CV_HD void cvd_insert(const CvDedupe &D, uint32_t i) {
     const uint32_t *k = D.pk + 8 * (size_t)i;
-    uint64_t slot = cvu_hash(k, D.seed) & D.mask, n = 0;
-    bool done = false;
-    while (n <= D.mask) {
-        n++;
+    // the relaxed look BEFORE the CAS, the CAS only when it read empty; atomicMin only when i < old (first occurrence)
+    const CvWalk<uint64_t> w = cv_walk(D.mask, cvu_hash(k, D.seed), nullptr, [&](uint64_t slot) {
         // A look before the read-modify-write: a batch of few keys sends thousands of lanes to one slot, and the
         // atomics of one address run one after another.  A slot, once claimed, keeps its key and only falls, so
         // whatever value the look gives, a holder with this lane's key at or below i means i cannot be the slot's
         // final value: nothing to do.
         uint32_t old = cvd_atomic_load(D.tab + slot);
         if (old == CVD_NONE) old = cvu_atomic_cas(D.tab + slot, CVD_NONE, i);
-        if (old == CVD_NONE) {
-            done = true;
-            break;
-        }
+        if (old == CVD_NONE) return true;
         // `old` may already have been lowered by another lane with the same key: any holder of the slot carries it
-        if (cvu_key_eq(D.pk + 8 * (size_t)old, k)) {
-            if (i < old) cvu_atomic_min(D.tab + slot, i);
-            done = true;
-            break;
-        }
-        slot = (slot + 1) & D.mask;
-    }
-    if (!done) D.stat[CVD_STAT_OK] = 0;         // more signatures than slots: the caller sized the table at twice
+        if (!cvu_key_eq(D.pk + 8 * (size_t)old, k)) return false;
+        if (i < old) cvu_atomic_min(D.tab + slot, i);
+        return true;
+    });
+    if (!w.stopped) D.stat[CVD_STAT_OK] = 0;    // more signatures than slots: the caller sized the table at twice
 }
 
 CV_HD void cvd_mark(const CvDedupe &D, uint32_t i) {
     const uint32_t *k = D.pk + 8 * (size_t)i;
-    uint64_t slot = cvu_hash(k, D.seed) & D.mask, n = 0;
-    uint32_t f = i;                             // after a probe error: a key of its own, every index in range
-    bool done = false;
-    while (n <= D.mask) {
-        n++;
+    uint32_t f = CVD_NONE;
+    // read-only, the o < D.n guard kept; an empty slot ends the walk WITHOUT a holder, an error as f > i is
+    cv_walk(D.mask, cvu_hash(k, D.seed), nullptr, [&](uint64_t slot) {
         const uint32_t o = D.tab[slot];
-        if (o == CVD_NONE) break;               // insert put the key before this slot: only after its probe error
-        if (o < D.n && cvu_key_eq(D.pk + 8 * (size_t)o, k)) {
-            f = o;
-            done = true;
-            break;
-        }
-        slot = (slot + 1) & D.mask;
-    }
-    if (!done || f > i) {
+        if (o == CVD_NONE) return true;         // insert put the key before this slot: only after its probe error
+        if (o >= D.n || !cvu_key_eq(D.pk + 8 * (size_t)o, k)) return false;
+        f = o;
+        return true;
+    });
+    if (f > i) {                                // no holder (CVD_NONE), or one after i: a key of its own, every index in range
         D.stat[CVD_STAT_OK] = 0;
         f = i;
     }
@@ -126,11 +104,7 @@ CV_HD void cvd_emit(const CvDedupe &D, uint32_t i) {
 // ---------------------------------------------------------------- host: the workspace
 #ifndef __HIP_DEVICE_COMPILE__
 // slots of the table: a power of two, at least 2 n (n < 2^32)
-inline uint64_t cvd_slots(uint64_t n) {
-    uint64_t s = 2;
-    while (s < 2 * n) s <<= 1;
-    return s;
-}
+inline uint64_t cvd_slots(uint64_t n) { return cv_table_slots(n, 2); }
 inline uint64_t cvd_blocks(uint64_t m) { return (m + CVD_SPAN - 1) / CVD_SPAN; }
 
 // Offsets into the workspace, each piece 16-byte aligned: table | stat | first | number | the levels' block sums

@@ -7,12 +7,11 @@
 // tests/keystore_harness.cpp runs the lanes on the CPU one after another, in any order (the atomics reduce to plain
 // operations there).
 //
-// THE STORE (CvKeyTable): open addressing, linear probing, a power-of-two slot count of at least twice the capacity.
-// occ (0 = empty, else the tag: a 32-bit fingerprint of the key's hash with bit 0 set) and, per slot, the expanded
-// record a | prefix | Abyte (24 words: the 96 bytes of a cv_signer record).  Abyte, the encoded public key, is what
-// the slot is found by: the identity of a key is its 32 encoded bytes.  Slot and tag come from cvu_hash's seeded mix
-// of all eight key words (a counterparty can grind the keys it asks a node to sign with, as it can state keys).
-// Nothing is ever deleted, so a probe ends at the first empty slot.
+// THE STORE (CvKeyTable): a table of cv_table.h (probing, sizing and hashing are described there) with a per-store
+// random seed and a floor of 16 slots.  occ (0 = empty, else the tag: a 32-bit fingerprint of the key's hash with bit
+// 0 set) and, per slot, the expanded record a | prefix | Abyte (24 words: the 96 bytes of a cv_signer record).  Abyte,
+// the encoded public key, is what the slot is found by: the identity of a key is its 32 encoded bytes (a counterparty
+// can grind the keys it asks a node to sign with, as it can state keys).
 //
 // ONE add (n seeds), a kernel per step:
 //   expand    per seed i: cv_key_expand -> the staged record i and pk[i]                        (cv_k_keystore.hip)
@@ -39,15 +38,16 @@
 // and a transaction that is not OK has every slot of its keys set to none, so its lanes leave the signing kernel
 // before they read a key record and its signatures are zero.
 //
-// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE LOOP IS BOUNDED by its table's slot count and
-// sets dstat[CKS_D_ERROR] when it runs out (the host returns CV_E_HIP); the capacity check rules it out.
+// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE IS BOUNDED: each is cv_walk (cv_table.h), which
+// looks at no more than its table's slot count, and sets dstat[CKS_D_ERROR] when it runs out (the host returns
+// CV_E_HIP); the capacity check rules it out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "cv_keydedupe.h"
 
-#define CKS_NONE 0xffffffffu       // no slot: the key is absent, or its transaction is abandoned
+#define CKS_NONE CVT_NONE          // no slot: the key is absent, or its transaction is abandoned
 #define CKS_REC_WORDS 24           // a | prefix | Abyte
 #define CKS_REC_A 0
 #define CKS_REC_PREFIX 8
@@ -62,8 +62,8 @@
 #define CKS_ST_ALREADY_SIGNED 2
 #define CKS_ST_EMPTY 3
 // words of the per-call device counters
-#define CKS_D_ERROR 0              // a probe loop ran out of slots
-#define CKS_D_MAXPROBE 1           // longest probe of the store (slots looked at)
+#define CKS_D_ERROR CVT_D_ERROR     // a probe ran out of slots
+#define CKS_D_MAXPROBE CVT_D_MAXPROBE   // longest probe of the store (slots looked at)
 #define CKS_D_ADDED 2              // records the call put
 #define CKS_D_WORDS 4
 
@@ -73,6 +73,14 @@ struct CvKeyTable {
     uint32_t mask;                 // slots - 1
     uint64_t seed;
 };
+#ifndef __HIP_DEVICE_COMPILE__
+// the table in ONE allocation of CKS_SLOT_BYTES * slots at base: occ | rec (16-byte aligned: slots >= 16)
+#define CKS_SLOT_BYTES (4 * (1 + CKS_REC_WORDS))
+inline CvKeyTable cks_carve(void *base, size_t slots, uint64_t seed) {
+    uint32_t *p = static_cast<uint32_t *>(base);
+    return CvKeyTable{p, p + slots, (uint32_t)(slots - 1), seed};
+}
+#endif
 
 // the builder's signing step: ntx transactions, transaction t signed by keys [sig_begin[t], sig_begin[t + 1])
 struct CvKeyTx {
@@ -90,48 +98,23 @@ struct CvKeyTx {
 
 // The slot holding `key`, or CKS_NONE.  Read-only.
 CV_HD uint32_t cks_find(const CvKeyTable &T, const uint32_t *key, uint32_t *dstat) {
-    const uint64_t h = cvu_hash(key, T.seed);
-    const uint32_t tag = cvu_tag(h);
-    uint32_t slot = (uint32_t)h & T.mask, found = CKS_NONE, n = 0;
-    bool done = false;
-    while (n <= T.mask) {
-        const uint32_t o = T.occ[slot];
-        n++;
-        if (o == 0) {
-            done = true;
-            break;
-        }
-        if (o == tag && cvu_key_eq(T.rec + CKS_REC_WORDS * (size_t)slot + CKS_REC_ABYTE, key)) {
-            found = slot;
-            done = true;
-            break;
-        }
-        slot = (slot + 1) & T.mask;
-    }
-    if (!done) dstat[CKS_D_ERROR] = 1;          // a full table without the key: the capacity check rules it out
-    cvu_note_max(dstat + CKS_D_MAXPROBE, n);
-    return found;
+    const uint32_t *rec = T.rec;
+    // the store counts NO wraps (word 2 of its counters is CKS_D_ADDED); max-probe and error as the set's
+    return cvt_find(
+        T.occ, T.mask, [rec](uint32_t slot) { return rec + CKS_REC_WORDS * (size_t)slot + CKS_REC_ABYTE; }, key,
+        cvu_hash(key, T.seed), dstat, nullptr);
 }
 
 // Puts a record whose key is absent and that no other lane inserts: the first slot this lane's CAS turns from empty.
 CV_HD void cks_insert(const CvKeyTable &T, const uint32_t *rec, uint32_t *dstat) {
-    const uint64_t h = cvu_hash(rec + CKS_REC_ABYTE, T.seed);
-    const uint32_t tag = cvu_tag(h);
-    uint32_t slot = (uint32_t)h & T.mask, n = 0;
-    bool done = false;
-    while (n <= T.mask) {
-        n++;
-        if (cvu_atomic_cas(T.occ + slot, 0u, tag) == 0u) {
-            uint32_t *d = T.rec + CKS_REC_WORDS * (size_t)slot;
+    // no wraps counted, as cks_find; an overflow sets CKS_D_ERROR and stores nothing
+    const CvWalk<uint32_t> w = cvt_claim(T.occ, T.mask, cvu_hash(rec + CKS_REC_ABYTE, T.seed), nullptr);
+    if (w.stopped) {
+        uint32_t *d = T.rec + CKS_REC_WORDS * (size_t)w.slot;
 #pragma unroll
-            for (int q = 0; q < CKS_REC_WORDS; q++) d[q] = rec[q];
-            done = true;
-            break;
-        }
-        slot = (slot + 1) & T.mask;
+        for (int q = 0; q < CKS_REC_WORDS; q++) d[q] = rec[q];
     }
-    if (!done) dstat[CKS_D_ERROR] = 1;
-    cvu_note_max(dstat + CKS_D_MAXPROBE, n);
+    cvt_note(dstat, w);
 }
 
 // growth: one lane per slot of the old table re-inserts its record into the new one

@@ -5,10 +5,9 @@
 // and the walk are plain host C++ below, the same code in the library, the harness and the sanitizer program.
 //
 // THREE KERNELS, no lane reading what another lane of its kernel writes except through an atomic:
-//   insert  per transaction t: atomicCAS(slot, NONE, t) into a batch-local open-addressing table of transaction
-//           INDICES over the CLAIMED ids (stx.id is what resultQ and forwardGraph are keyed by, :39-45,:170): a
-//           power-of-two slot count of at least 2 ntx, linear probing, the slot from cvu_hash's seeded mix of all eight
-//           id words (ids are hashes the serving peer can grind: no id bits choose a slot directly).  A loser compares
+//   insert  per transaction t: atomicCAS(slot, NONE, t) into a batch-local table of transaction INDICES over the
+//           CLAIMED ids (stx.id is what resultQ and forwardGraph are keyed by, :39-45,:170): a table of cv_table.h
+//           (probing, sizing and hashing are described there; a floor of 2 slots).  A loser compares
 //           its id with the occupant's — both in the immutable input — and probes on, or, on equality, does
 //           atomicMin(slot, t) and atomicMin(dstat[DUP], min(t, occupant)): the slot ends at the smallest index that
 //           carries the id and DUP at the smallest index whose id occurs more than once, whichever lane won.
@@ -25,8 +24,8 @@
 //             MALFORMED, SIGNATURES_MISSING   the missing-signers status (cv_ck.h), no key allowed to be missing
 //             BAD_INPUT                some input's status is 2; bad_input[t] = the first such input
 //           atomicMin(dstat[BADID], t) for EMPTY / ID_MISMATCH; the external inputs are added to dstat[EXTERNAL].
-// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE LOOP IS BOUNDED by the slot count and sets
-// dstat[CVR_D_ERROR] when it runs out (the host returns CV_E_HIP).
+// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE IS BOUNDED: each is cv_walk (cv_table.h), which
+// looks at no more than the slot count, and sets dstat[CVR_D_ERROR] when it runs out (the host returns CV_E_HIP).
 //
 // HOST, after the one read-back (a lexicographic depth-first order is inherently sequential):
 //   cvr_order  topologicalSort (:37-67): the dependents of every transaction — distinct, in ascending index order,
@@ -108,50 +107,35 @@ struct CvResolve {
 
 CV_HD void cvr_insert(const CvResolve &R, uint32_t t) {
     const uint32_t *k = R.claimed + 8 * (size_t)t;
-    uint32_t slot = (uint32_t)cvu_hash(k, R.seed) & R.mask, n = 0;
-    bool done = false;
-    while (n <= R.mask) {
-        n++;
+    // the CAS first; on an equal id atomicMin on the slot unconditionally and on CVR_D_DUP; wraps and max-probe counted
+    uint32_t *const wraps = R.dstat + CVR_D_WRAPS;
+    const CvWalk<uint32_t> w = cv_walk(R.mask, (uint32_t)cvu_hash(k, R.seed), wraps, [&](uint32_t slot) {
         const uint32_t old = cvu_atomic_cas(R.tab + slot, CVR_NONE, t);
-        if (old == CVR_NONE) {
-            done = true;
-            break;
-        }
+        if (old == CVR_NONE) return true;
         // `old` may already have been lowered by another loser of the same id: any holder of the slot carries that id
-        if (cvu_key_eq(R.claimed + 8 * (size_t)old, k)) {
-            cvu_atomic_min(R.tab + slot, t);
-            cvu_atomic_min(R.dstat + CVR_D_DUP, t < old ? t : old);
-            done = true;
-            break;
-        }
-        if (slot == R.mask) cvu_atomic_add(R.dstat + CVR_D_WRAPS, 1);
-        slot = (slot + 1) & R.mask;
-    }
-    if (!done) R.dstat[CVR_D_ERROR] = 1;        // more transactions than slots: the caller sized the table at twice
-    cvu_note_max(R.dstat + CVR_D_MAXPROBE, n);
+        if (!cvu_key_eq(R.claimed + 8 * (size_t)old, k)) return false;
+        cvu_atomic_min(R.tab + slot, t);
+        cvu_atomic_min(R.dstat + CVR_D_DUP, t < old ? t : old);
+        return true;
+    });
+    if (!w.stopped) R.dstat[CVR_D_ERROR] = 1;   // more transactions than slots: the caller sized the table at twice
+    cvu_note_max(R.dstat + CVR_D_MAXPROBE, w.n);
 }
 
 CV_HD void cvr_probe(const CvResolve &R, uint32_t i) {
     const uint32_t *k = R.input_txhash + 8 * (size_t)i;
-    uint32_t slot = (uint32_t)cvu_hash(k, R.seed) & R.mask, n = 0, dep = CVR_NONE;
-    bool done = false;
-    while (n <= R.mask) {
-        n++;
+    uint32_t dep = CVR_NONE;
+    // read-only, the o < R.ntx guard kept; wraps and max-probe counted
+    uint32_t *const wraps = R.dstat + CVR_D_WRAPS;
+    const CvWalk<uint32_t> w = cv_walk(R.mask, (uint32_t)cvu_hash(k, R.seed), wraps, [&](uint32_t slot) {
         const uint32_t o = R.tab[slot];
-        if (o == CVR_NONE) {
-            done = true;
-            break;
-        }
-        if (o < R.ntx && cvu_key_eq(R.claimed + 8 * (size_t)o, k)) {
-            dep = o;
-            done = true;
-            break;
-        }
-        if (slot == R.mask) cvu_atomic_add(R.dstat + CVR_D_WRAPS, 1);
-        slot = (slot + 1) & R.mask;
-    }
-    if (!done) R.dstat[CVR_D_ERROR] = 1;        // a full table without the id: the slot count rules it out
-    cvu_note_max(R.dstat + CVR_D_MAXPROBE, n);
+        if (o == CVR_NONE) return true;
+        if (o >= R.ntx || !cvu_key_eq(R.claimed + 8 * (size_t)o, k)) return false;
+        dep = o;
+        return true;
+    });
+    if (!w.stopped) R.dstat[CVR_D_ERROR] = 1;   // a full table without the id: the slot count rules it out
+    cvu_note_max(R.dstat + CVR_D_MAXPROBE, w.n);
     R.input_dep[i] = dep;
     R.input_status[i] = dep == CVR_NONE ? CVR_IN_EXTERNAL : R.input_index[i] < R.tx_output_count[dep] ? CVR_IN_OK : CVR_IN_RANGE;
 }
@@ -202,11 +186,7 @@ CV_HD void cvr_gate(const CvResolve &R, uint32_t t) {
 #include <vector>
 
 // slots of the join table: a power of two, at least 2 ntx (ntx <= 2^30)
-inline uint32_t cvr_slots(size_t ntx) {
-    uint32_t s = 2;
-    while ((size_t)s < 2 * ntx) s <<= 1;
-    return s;
-}
+inline uint32_t cvr_slots(size_t ntx) { return (uint32_t)cv_table_slots(ntx, 2); }
 
 // topologicalSort over input_dep; order gets ntx entries.  No two transactions share an id (the caller checked).
 inline void cvr_order(uint32_t ntx, const uint32_t *tx_input_begin, const uint32_t *input_dep, uint32_t *order) {

@@ -5,11 +5,9 @@
 // cv_k_uniq.hip; __host__ __device__, so tests/uniq_harness.cpp runs the lanes on the CPU one after another, in any
 // order (the atomics reduce to plain operations there).
 //
-// RESIDENT TABLE (CvUniqTable): open addressing, linear probing, a power-of-two slot count of at least twice the
-// capacity, structure of arrays: occ (0 = empty, else the tag: a 32-bit fingerprint of the key's hash with bit 0
-// set), key (8 words), id (8 words), index, caller.  The slot and the tag come from a 64-bit multiply-xorshift mix
-// of all eight key words with a per-set random seed: keys are SHA-256 outputs a submitter can grind, so no key bits
-// choose the slot directly.  Nothing is ever deleted, so a probe ends at the first empty slot.
+// RESIDENT TABLE (CvUniqTable): a table of cv_table.h (probing, sizing and hashing are described there) with a
+// per-set random seed and a floor of 16 slots, structure of arrays: occ (0 = empty, else the tag: a 32-bit fingerprint
+// of the key's hash with bit 0 set), key (8 words), id (8 words), index, caller.
 //
 // ONE commit_batch (ntx requests, request t holding states [begin[t], begin[t + 1])), a kernel per step:
 //   init    per request: stat = UNDECIDED, or REJECTED when its enable byte is 0; state_tx of its states
@@ -45,17 +43,16 @@
 // The records are a function of the table and the window alone.  INSTALL builds a fresh table with the load path
 // (cvu_group with stat == null, cvu_load_check, cvu_load_put) and the host swaps the tables; CLEAR zeroes occ.
 //
-// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE LOOP IS BOUNDED by its table's slot count and
-// sets dstat[CVU_D_ERROR] when it runs out (the host returns CV_E_HIP).
+// NO LANE WAITS FOR ANOTHER LANE: no spin, lock or flag.  EVERY PROBE IS BOUNDED: each is cv_walk (cv_table.h), which
+// looks at no more than its table's slot count, and sets dstat[CVU_D_ERROR] when it runs out (the host returns
+// CV_E_HIP).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef CV_HD
-#define CV_HD __host__ __device__ __forceinline__
-#endif
+#include "cv_table.h"
 
-#define CVU_NONE 0xffffffffu      // empty batch slot, no owner, not resident
+#define CVU_NONE CVT_NONE         // empty batch slot, no owner, not resident
 #define CVU_UNDECIDED 0u
 #define CVU_ACCEPTED 1u
 #define CVU_REJECTED 2u
@@ -64,8 +61,8 @@
 #define CVU_CONFLICT 1
 #define CVU_SKIPPED 2
 // words of the per-call device counters
-#define CVU_D_ERROR 0             // a probe loop ran out of slots
-#define CVU_D_MAXPROBE 1          // longest probe of the resident table (slots looked at)
+#define CVU_D_ERROR CVT_D_ERROR    // a probe ran out of slots
+#define CVU_D_MAXPROBE CVT_D_MAXPROBE   // longest probe of the resident table (slots looked at)
 #define CVU_D_WRAPS 2             // probes of the resident table that passed its last slot
 #define CVU_D_INSERTED 3
 #define CVU_D_TAIL 4              // requests the serial tail decided
@@ -79,6 +76,14 @@ struct CvUniqTable {
     uint32_t mask;                // slots - 1
     uint64_t seed;
 };
+#ifndef __HIP_DEVICE_COMPILE__
+// the table in ONE allocation of CVU_SLOT_BYTES * slots at base: occ | key | id | index | caller
+#define CVU_SLOT_BYTES 76
+inline CvUniqTable cvu_carve(void *base, size_t slots, uint64_t seed) {
+    uint32_t *p = static_cast<uint32_t *>(base);
+    return CvUniqTable{p, p + slots, p + 9 * slots, p + 17 * slots, p + 18 * slots, (uint32_t)(slots - 1), seed};
+}
+#endif
 
 // words of a snapshot call's device result
 #define CVU_SNAP_NEXT 0           // the slot the next call starts at (slot_end: the window is done)
@@ -107,114 +112,26 @@ struct CvUniqBatch {
     uint32_t *dstat;              // CVU_D_WORDS
 };
 
-CV_HD uint32_t cvu_atomic_cas(uint32_t *p, uint32_t expect, uint32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return atomicCAS(p, expect, v);
-#else
-    const uint32_t old = *p;
-    if (old == expect) *p = v;
-    return old;
-#endif
-}
-CV_HD void cvu_atomic_min(uint32_t *p, uint32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    atomicMin(p, v);
-#else
-    if (v < *p) *p = v;
-#endif
-}
-CV_HD void cvu_atomic_add(uint32_t *p, uint32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    atomicAdd(p, v);
-#else
-    *p += v;
-#endif
-}
-// a running maximum: the plain read first spares most lanes the atomic (the word only grows)
-CV_HD void cvu_note_max(uint32_t *p, uint32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    if (v > *p) atomicMax(p, v);
-#else
-    if (v > *p) *p = v;
-#endif
-}
-
-CV_HD uint64_t cvu_mix64(uint64_t x) {
-    x ^= x >> 32;
-    x *= 0xd6e8feb86659fd93ull;
-    x ^= x >> 29;
-    x *= 0x9e3779b97f4a7c15ull;
-    x ^= x >> 32;
-    return x;
-}
-
-// all eight key words folded with the seed; the low bits choose the slot, the high word is the fingerprint
-CV_HD uint64_t cvu_hash(const uint32_t *k, uint64_t seed) {
-    uint64_t h = seed;
-#pragma unroll
-    for (int q = 0; q < 4; q++) h = cvu_mix64(h ^ ((uint64_t)k[2 * q] | ((uint64_t)k[2 * q + 1] << 32))) + seed;
-    return h;
-}
-CV_HD uint32_t cvu_tag(uint64_t h) { return (uint32_t)(h >> 32) | 1u; }
-
-CV_HD bool cvu_key_eq(const uint32_t *a, const uint32_t *b) {
-    uint32_t diff = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) diff |= a[q] ^ b[q];
-    return diff == 0;
-}
-CV_HD void cvu_copy8(uint32_t *d, const uint32_t *s) {
-#pragma unroll
-    for (int q = 0; q < 8; q++) d[q] = s[q];
-}
-
 // The slot holding `key`, or CVU_NONE.  Read-only.
 CV_HD uint32_t cvu_find(const CvUniqTable &T, const uint32_t *key, uint64_t h, uint32_t *dstat) {
-    const uint32_t tag = cvu_tag(h);
-    uint32_t slot = (uint32_t)h & T.mask, found = CVU_NONE, n = 0;
-    bool done = false;
-    while (n <= T.mask) {
-        const uint32_t o = T.occ[slot];
-        n++;
-        if (o == 0) {
-            done = true;
-            break;
-        }
-        if (o == tag && cvu_key_eq(T.key + 8 * (size_t)slot, key)) {
-            found = slot;
-            done = true;
-            break;
-        }
-        if (slot == T.mask) cvu_atomic_add(dstat + CVU_D_WRAPS, 1);
-        slot = (slot + 1) & T.mask;
-    }
-    if (!done) dstat[CVU_D_ERROR] = 1;          // a full table without the key: the capacity check rules it out
-    cvu_note_max(dstat + CVU_D_MAXPROBE, n);
-    return found;
+    const uint32_t *keys = T.key;
+    // the set counts wraps into CVU_D_WRAPS beside max-probe and error; the tag is compared before the key
+    return cvt_find(T.occ, T.mask, [keys](uint32_t slot) { return keys + 8 * (size_t)slot; }, key, h, dstat,
+                    dstat + CVU_D_WRAPS);
 }
 
 // Puts a key that is absent and that no other lane inserts: the first slot this lane's CAS turns from empty.
 CV_HD void cvu_insert(const CvUniqTable &T, const uint32_t *key, const uint32_t *id, uint32_t index, uint32_t caller,
                       uint32_t *dstat) {
-    const uint64_t h = cvu_hash(key, T.seed);
-    const uint32_t tag = cvu_tag(h);
-    uint32_t slot = (uint32_t)h & T.mask, n = 0;
-    bool done = false;
-    while (n <= T.mask) {
-        n++;
-        if (cvu_atomic_cas(T.occ + slot, 0u, tag) == 0u) {
-            cvu_copy8(T.key + 8 * (size_t)slot, key);
-            cvu_copy8(T.id + 8 * (size_t)slot, id);
-            T.index[slot] = index;
-            T.caller[slot] = caller;
-            done = true;
-            break;
-        }
-        if (slot == T.mask) cvu_atomic_add(dstat + CVU_D_WRAPS, 1);
-        slot = (slot + 1) & T.mask;
+    // counts wraps into CVU_D_WRAPS as cvu_find does; an overflow sets CVU_D_ERROR and stores nothing
+    const CvWalk<uint32_t> w = cvt_claim(T.occ, T.mask, cvu_hash(key, T.seed), dstat + CVU_D_WRAPS);
+    if (w.stopped) {
+        cvu_copy8(T.key + 8 * (size_t)w.slot, key);
+        cvu_copy8(T.id + 8 * (size_t)w.slot, id);
+        T.index[w.slot] = index;
+        T.caller[w.slot] = caller;
     }
-    if (!done) dstat[CVU_D_ERROR] = 1;
-    cvu_note_max(dstat + CVU_D_MAXPROBE, n);
+    cvt_note(dstat, w);
 }
 
 // growth: one lane per slot of the old table re-inserts its record into the new one
@@ -245,20 +162,16 @@ CV_HD void cvu_init(const CvUniqBatch &B, uint32_t *stat, uint32_t t) {
 CV_HD void cvu_group(const CvUniqTable &T, const CvUniqBatch &B, uint32_t *stat, uint32_t i) {
     const uint32_t *k = B.key + 8 * (size_t)i;
     const uint64_t h = cvu_hash(k, T.seed);
-    uint32_t slot = (uint32_t)(h >> 20) & B.bmask, rep = CVU_NONE, n = 0;
-    while (n <= B.bmask) {
-        n++;
+    uint32_t rep = CVU_NONE;
+    // from bits 20.. of the resident find's h; a plain CAS, ANY winner is the representative; no wraps, no max-probe
+    cv_walk(B.bmask, (uint32_t)(h >> 20), nullptr, [&](uint32_t slot) {
         const uint32_t old = cvu_atomic_cas(B.btab + slot, CVU_NONE, i);
-        if (old == CVU_NONE) {
+        if (old == CVU_NONE)
             rep = i;
-            break;
-        }
-        if (cvu_key_eq(B.key + 8 * (size_t)old, k)) {
+        else if (cvu_key_eq(B.key + 8 * (size_t)old, k))
             rep = old;
-            break;
-        }
-        slot = (slot + 1) & B.bmask;
-    }
+        return rep != CVU_NONE;
+    });
     if (rep == CVU_NONE) {                      // more states than slots: the caller sized the table at twice the states
         B.dstat[CVU_D_ERROR] = 1;
         rep = i;
@@ -368,14 +281,6 @@ CV_HD void cvu_load_put(const CvUniqTable &T, const CvUniqBatch &B, uint32_t i) 
 // ---- snapshot: the per-lane pieces of count and emit (the header comment); the scan between them is the caller's
 CV_HD uint32_t cvu_snap_occupied(const CvUniqTable &T, const CvUniqSnap &S, uint32_t i) {
     return i < S.slot_end - S.slot_begin && T.occ[S.slot_begin + i] != 0;
-}
-// eight words between 16-byte aligned places (a table's arrays and a call's buffers are): two 16-byte moves on the device
-CV_HD void cvu_copy8_aligned(uint32_t *d, const uint32_t *s) {
-#ifdef __HIP_DEVICE_COMPILE__
-    d = static_cast<uint32_t *>(__builtin_assume_aligned(d, 16));
-    s = static_cast<const uint32_t *>(__builtin_assume_aligned(s, 16));
-#endif
-    cvu_copy8(d, s);
 }
 // lane i of the window holds an occupied slot, the rank-th of the window
 CV_HD void cvu_snap_emit(const CvUniqTable &T, const CvUniqSnap &S, uint32_t i, uint32_t rank) {

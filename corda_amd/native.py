@@ -1028,90 +1028,16 @@ class Engine:
         _check(self._lib.cv_synchronize(self._h, device), "cv_synchronize")
 
 
-class Signer:
-    """One Ed25519 key bound to an engine (cv_signer): the key is expanded once on every device, then
-    sign() / sign_device() sign batches with it — KeyPair.signWithECDSA (CryptoUtilities.kt:63-73) for a
-    holder of one long-lived key, such as a notary.  Immutable after construction: several threads may sign
-    with it at once.  close() (or the with-statement) wipes the device records; the engine closes the
-    signers still open when it is closed itself."""
+class _Handle:
+    """The life of a native handle bound to an engine: close() once (and again without effect), the with-statement,
+    the finaliser, and _open(), which hands the handle out or says that it is closed.  A subclass names its close
+    entry point and itself, sets _engine, _lib and _h, and adds itself to engine._signers."""
 
-    def __init__(self, engine: Engine, seed):
-        seed = np.frombuffer(bytes(seed), np.uint8)
-        if seed.size != 32:
-            raise ValueError("seed must be 32 bytes")
-        self._engine = engine
-        self._lib = engine._lib
-        h = _vp()
-        _check(self._lib.cv_signer_open(engine._h, _p(seed), ctypes.byref(h)), "cv_signer_open")
-        self._h = h
-        pk = np.zeros(32, np.uint8)
-        _check(self._lib.cv_signer_public_key(h, _p(pk)), "cv_signer_public_key")
-        self.public_key = pk.tobytes()
-        engine._signers.add(self)
+    _close_fn = _what = None
 
     def close(self):
         if self._h:
-            self._lib.cv_signer_close(self._h)
-            self._h = None
-            self._engine._signers.discard(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def sign(self, arena, off, ln) -> np.ndarray:
-        """arena u8, off u64[n], ln u32[n] -> sig (n,64) u8, one signature per message, in one call."""
-        if not self._h:
-            raise ValueError("the signer is closed")
-        arena = _u8(arena) if arena is not None and np.asarray(arena).size else np.zeros(16, np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        ln = np.ascontiguousarray(ln, dtype=np.uint32)
-        n = off.shape[0]
-        if ln.shape[0] != n:
-            raise ValueError("off/len must have n entries")
-        sig = np.zeros((n, 64), np.uint8)
-        rc = self._lib.cv_ed25519_sign_keyed(self._engine._h, self._h, n, _p(arena), arena.size, _p(off), _p(ln),
-                                             _p(sig))
-        if rc == -3 and n and _msg_end(self._lib, off, ln) > arena.size:
-            raise ValueError("message range exceeds the arena")
-        _check(rc, "cv_ed25519_sign_keyed")
-        return sig
-
-    def sign_device(self, device: int, n: int, d_arena: int, d_off: int, d_len: int, d_sig: int, stream: int = 0):
-        """Device pointers in, d_sig[n][64] out; enqueued on stream (0: the device's own), not synchronised."""
-        if not self._h:
-            raise ValueError("the signer is closed")
-        _check(self._lib.cv_ed25519_sign_keyed_device(self._engine._h, device, self._h, n, d_arena, d_off, d_len,
-                                                      d_sig, stream or None), "cv_ed25519_sign_keyed_device")
-
-
-class KeyStore:
-    """A device-resident store of expanded private keys addressed by public key, bound to an engine (cv_keystore): the
-    node's KeyManagementService (Services.kt:206-219, PersistentKeyManagementService.kt:40-66) — add() is freshKey() for
-    a batch of seeds, contains() is keys.contains, sign() is KeyPair(pk, toPrivate(pk)).signWithECDSA with every record
-    naming its own key, sign_transactions() the builder's signing step (TransactionBuilder.kt:93-98,132-141) for a
-    batch.  No call gives out a private half.  Calls serialise on the store's own lock.  close() (or the
-    with-statement) overwrites and frees the table; the engine closes the stores still open when it is closed itself."""
-
-    def __init__(self, engine: Engine, capacity: int, device: int = 0):
-        self._engine = engine
-        self._lib = engine._lib
-        h = _vp()
-        _check(self._lib.cv_keystore_open(engine._h, device, int(capacity), ctypes.byref(h)), "cv_keystore_open")
-        self._h = h
-        engine._signers.add(self)
-
-    def close(self):
-        if self._h:
-            self._lib.cv_keystore_close(self._h)
+            getattr(self._lib, self._close_fn)(self._h)
             self._h = None
             self._engine._signers.discard(self)
 
@@ -1129,8 +1055,74 @@ class KeyStore:
 
     def _open(self):
         if not self._h:
-            raise ValueError("the key store is closed")
+            raise ValueError(f"the {self._what} is closed")
         return self._h
+
+
+class Signer(_Handle):
+    """One Ed25519 key bound to an engine (cv_signer): the key is expanded once on every device, then
+    sign() / sign_device() sign batches with it — KeyPair.signWithECDSA (CryptoUtilities.kt:63-73) for a
+    holder of one long-lived key, such as a notary.  Immutable after construction: several threads may sign
+    with it at once.  close() (or the with-statement) wipes the device records; the engine closes the
+    signers still open when it is closed itself."""
+
+    _close_fn, _what = "cv_signer_close", "signer"
+
+    def __init__(self, engine: Engine, seed):
+        seed = np.frombuffer(bytes(seed), np.uint8)
+        if seed.size != 32:
+            raise ValueError("seed must be 32 bytes")
+        self._engine = engine
+        self._lib = engine._lib
+        h = _vp()
+        _check(self._lib.cv_signer_open(engine._h, _p(seed), ctypes.byref(h)), "cv_signer_open")
+        self._h = h
+        pk = np.zeros(32, np.uint8)
+        _check(self._lib.cv_signer_public_key(h, _p(pk)), "cv_signer_public_key")
+        self.public_key = pk.tobytes()
+        engine._signers.add(self)
+
+    def sign(self, arena, off, ln) -> np.ndarray:
+        """arena u8, off u64[n], ln u32[n] -> sig (n,64) u8, one signature per message, in one call."""
+        self._open()
+        arena = _u8(arena) if arena is not None and np.asarray(arena).size else np.zeros(16, np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        ln = np.ascontiguousarray(ln, dtype=np.uint32)
+        n = off.shape[0]
+        if ln.shape[0] != n:
+            raise ValueError("off/len must have n entries")
+        sig = np.zeros((n, 64), np.uint8)
+        rc = self._lib.cv_ed25519_sign_keyed(self._engine._h, self._h, n, _p(arena), arena.size, _p(off), _p(ln),
+                                             _p(sig))
+        if rc == -3 and n and _msg_end(self._lib, off, ln) > arena.size:
+            raise ValueError("message range exceeds the arena")
+        _check(rc, "cv_ed25519_sign_keyed")
+        return sig
+
+    def sign_device(self, device: int, n: int, d_arena: int, d_off: int, d_len: int, d_sig: int, stream: int = 0):
+        """Device pointers in, d_sig[n][64] out; enqueued on stream (0: the device's own), not synchronised."""
+        self._open()
+        _check(self._lib.cv_ed25519_sign_keyed_device(self._engine._h, device, self._h, n, d_arena, d_off, d_len,
+                                                      d_sig, stream or None), "cv_ed25519_sign_keyed_device")
+
+
+class KeyStore(_Handle):
+    """A device-resident store of expanded private keys addressed by public key, bound to an engine (cv_keystore): the
+    node's KeyManagementService (Services.kt:206-219, PersistentKeyManagementService.kt:40-66) — add() is freshKey() for
+    a batch of seeds, contains() is keys.contains, sign() is KeyPair(pk, toPrivate(pk)).signWithECDSA with every record
+    naming its own key, sign_transactions() the builder's signing step (TransactionBuilder.kt:93-98,132-141) for a
+    batch.  No call gives out a private half.  Calls serialise on the store's own lock.  close() (or the
+    with-statement) overwrites and frees the table; the engine closes the stores still open when it is closed itself."""
+
+    _close_fn, _what = "cv_keystore_close", "key store"
+
+    def __init__(self, engine: Engine, capacity: int, device: int = 0):
+        self._engine = engine
+        self._lib = engine._lib
+        h = _vp()
+        _check(self._lib.cv_keystore_open(engine._h, device, int(capacity), ctypes.byref(h)), "cv_keystore_open")
+        self._h = h
+        engine._signers.add(self)
 
     def add(self, seeds):
         """cv_keystore_add: seeds (n,32) u8 -> (pk (n,32) u8, status u8[n]: CV_KS_ADDED | CV_KS_PRESENT).  CvError with
@@ -1200,12 +1192,14 @@ class KeyStore:
         return dict(zip(CV_KS_STATS, map(int, out)))
 
 
-class UniquenessSet:
+class UniquenessSet(_Handle):
     """A device-resident set of consumed states bound to an engine (cv_uniq): the notary's commit step,
     UniquenessProvider.commit (UniquenessProvider.kt:13-35) as InMemoryUniquenessProvider.kt:14-36 decides it, for
     a whole batch in one call.  Keys are 32 bytes, a consuming record is (tx id[32], input index u32, caller u32).
     Calls serialise on the set's own lock.  close() (or the with-statement) frees the table; the engine closes the
     sets still open when it is closed itself."""
+
+    _close_fn, _what = "cv_uniq_close", "uniqueness set"
 
     def __init__(self, engine: Engine, capacity: int, device: int = 0):
         self._engine = engine
@@ -1214,29 +1208,6 @@ class UniquenessSet:
         _check(self._lib.cv_uniq_open(engine._h, device, int(capacity), ctypes.byref(h)), "cv_uniq_open")
         self._h = h
         engine._signers.add(self)
-
-    def close(self):
-        if self._h:
-            self._lib.cv_uniq_close(self._h)
-            self._h = None
-            self._engine._signers.discard(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _open(self):
-        if not self._h:
-            raise ValueError("the uniqueness set is closed")
-        return self._h
 
     def commit_batch(self, state_key, tx_state_begin, tx_id, caller, tx_enable=None, out=None):
         """cv_uniq_commit_batch: state_key (nstates,32) u8 cut by tx_state_begin u32[ntx+1], tx_id (ntx,32) u8,

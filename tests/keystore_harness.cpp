@@ -24,18 +24,11 @@ struct HStore {
     uint64_t probe = 0;
 };
 
-size_t slots_for(size_t capacity) {
-    size_t s = 16;
-    while (s < 2 * capacity) s <<= 1;
-    return s;
-}
-
-void carve(std::vector<uint32_t> &mem, size_t slots, uint64_t seed, CvKeyTable *T) {
-    mem.assign((1 + CKS_REC_WORDS) * slots, 0);
-    T->occ = mem.data();
-    T->rec = mem.data() + slots;
-    T->mask = (uint32_t)(slots - 1);
-    T->seed = seed;
+// a zeroed table for `capacity` keys in mem: the library's size (cv_table.h) and carve-up (cv_keystore.h)
+void carve(std::vector<uint32_t> &mem, size_t capacity, uint64_t seed, CvKeyTable *T) {
+    const size_t slots = (size_t)cv_table_slots(capacity, 16);
+    mem.assign(CKS_SLOT_BYTES * slots / 4, 0);
+    *T = cks_carve(mem.data(), slots, seed);
 }
 
 std::vector<uint32_t> lanes(size_t n, int order) {
@@ -63,7 +56,7 @@ extern "C" {
 void *hks_open(uint64_t capacity, uint64_t seed) {
     HStore *h = new HStore();
     h->capacity = capacity ? capacity : 1;
-    carve(h->mem, slots_for(h->capacity), seed, &h->T);
+    carve(h->mem, h->capacity, seed, &h->T);
     return h;
 }
 
@@ -78,13 +71,13 @@ void hks_stats(void *p, uint64_t out[4]) {
 int hks_reserve(void *p, uint64_t capacity, int order) {
     HStore *h = static_cast<HStore *>(p);
     if (capacity <= h->capacity) return 0;
-    if (slots_for(capacity) == (size_t)h->T.mask + 1) {
+    if (cv_table_slots(capacity, 16) == (uint64_t)h->T.mask + 1) {
         h->capacity = capacity;
         return 0;
     }
     std::vector<uint32_t> mem;
     CvKeyTable to{};
-    carve(mem, slots_for(capacity), h->T.seed, &to);
+    carve(mem, capacity, h->T.seed, &to);
     uint32_t dstat[CKS_D_WORDS] = {};
     for (uint32_t s : lanes((size_t)h->T.mask + 1, order)) cks_rehash(h->T, to, s, dstat);
     const int rc = fold(h, dstat);

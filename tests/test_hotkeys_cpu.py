@@ -24,8 +24,8 @@ LAYOUT = ("dedupe", "keys", "key_index", "nkeys", "count", "cand", "cls", "stat"
 
 
 def _deps(*srcs):
-    return list(srcs) + [os.path.join(CSRC, h) for h in ("cv_hotkeys.h", "cv_keydedupe.h", "cv_uniq.h")] + [
-        os.path.join(REPO, "tests", "keydedupe_harness.cpp")]
+    heads = ("cv_hotkeys.h", "cv_keydedupe.h", "cv_uniq.h", "cv_table.h")
+    return list(srcs) + [os.path.join(CSRC, h) for h in heads] + [os.path.join(REPO, "tests", "keydedupe_harness.cpp")]
 
 
 def _stale(target, deps):

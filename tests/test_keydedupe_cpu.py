@@ -23,7 +23,7 @@ POISON = 0xEE
 
 
 def _deps(*srcs):
-    return list(srcs) + [os.path.join(CSRC, h) for h in ("cv_keydedupe.h", "cv_uniq.h")]
+    return list(srcs) + [os.path.join(CSRC, h) for h in ("cv_keydedupe.h", "cv_uniq.h", "cv_table.h")]
 
 
 def _stale(target, deps):

@@ -192,6 +192,7 @@ def test_full_small_table_wraps_and_finds_every_key(harness, keys):
         assert st.tolist() == [K.KS_ADDED] * 8
         slot, _ = s.lookup(pks)
         assert 15 in [int(slot[i]) for i in last] and any(int(slot[i]) < 8 for i in last)      # the probe wrapped
+        assert s.stats()["resident"] == 8                           # a wrap is not counted: word 2 is the added count
         _check_records(s, keys[:8])
         assert s.stats()["probe"] >= 2
         rc, pk, st = s.add_rc([keys[8][0]], fill=0xEE)

@@ -23,7 +23,7 @@ CSRC = os.path.join(REPO, "corda_amd", "csrc")
 
 
 def _deps(*srcs):
-    return list(srcs) + [os.path.join(CSRC, h) for h in ("cv_resolve.h", "cv_notary.h", "cv_uniq.h")]
+    return list(srcs) + [os.path.join(CSRC, h) for h in ("cv_resolve.h", "cv_notary.h", "cv_uniq.h", "cv_table.h")]
 
 
 def _stale(target, deps):

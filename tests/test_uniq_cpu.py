@@ -22,7 +22,7 @@ ORDERS = (0, 1, 2)              # the harness's lane orders: ascending, descendi
 
 
 def _deps(*srcs):
-    return list(srcs) + [os.path.join(REPO, "corda_amd", "csrc", "cv_uniq.h")]
+    return list(srcs) + [os.path.join(REPO, "corda_amd", "csrc", h) for h in ("cv_uniq.h", "cv_table.h")]
 
 
 def _stale(target, deps):

@@ -20,7 +20,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 ORDERS = (0, 1, 2)
 DONE = 0xFFFFFFFFFFFFFFFF
 HARNESS = [os.path.join(REPO, "tests", "uniq_snapshot_harness.cpp"), os.path.join(REPO, "tests", "uniq_harness.cpp"),
-           os.path.join(REPO, "corda_amd", "csrc", "cv_uniq.h")]
+           os.path.join(REPO, "corda_amd", "csrc", "cv_uniq.h"), os.path.join(REPO, "corda_amd", "csrc", "cv_table.h")]
 
 
 def _stale(target, deps):

@@ -21,22 +21,11 @@ struct HSet {
     uint64_t rounds = 0, tail = 0, probe = 0, wraps = 0;
 };
 
-size_t slots_for(size_t capacity) {
-    size_t s = 16;
-    while (s < 2 * capacity) s <<= 1;
-    return s;
-}
-
-void carve(std::vector<uint32_t> &mem, size_t slots, uint64_t seed, CvUniqTable *T) {
-    mem.assign(19 * slots, 0);
-    uint32_t *p = mem.data();
-    T->occ = p;
-    T->key = p + slots;
-    T->id = p + 9 * slots;
-    T->index = p + 17 * slots;
-    T->caller = p + 18 * slots;
-    T->mask = (uint32_t)(slots - 1);
-    T->seed = seed;
+// a zeroed table for `capacity` states in mem: the library's size (cv_table.h) and carve-up (cv_uniq.h)
+void carve(std::vector<uint32_t> &mem, size_t capacity, uint64_t seed, CvUniqTable *T) {
+    const size_t slots = (size_t)cv_table_slots(capacity, 16);
+    mem.assign(CVU_SLOT_BYTES * slots / 4, 0);
+    *T = cvu_carve(mem.data(), slots, seed);
 }
 
 std::vector<uint32_t> lanes(size_t n, int order) {
@@ -58,12 +47,6 @@ int fold(HSet *h, const uint32_t *dstat) {
     return dstat[CVU_D_ERROR] ? -2 : 0;
 }
 
-uint32_t bmask_for(size_t n) {
-    size_t s = 16;
-    while (s < 2 * n) s <<= 1;
-    return (uint32_t)(s - 1);
-}
-
 }  // namespace
 
 extern "C" {
@@ -71,7 +54,7 @@ extern "C" {
 void *huq_open(uint64_t capacity, uint64_t seed) {
     HSet *h = new HSet();
     h->capacity = capacity ? capacity : 1;
-    carve(h->mem, slots_for(h->capacity), seed, &h->T);
+    carve(h->mem, h->capacity, seed, &h->T);
     return h;
 }
 
@@ -86,13 +69,13 @@ void huq_stats(void *p, uint64_t out[7]) {
 int huq_reserve(void *p, uint64_t capacity, int order) {
     HSet *h = static_cast<HSet *>(p);
     if (capacity <= h->capacity) return 0;
-    if (slots_for(capacity) == (size_t)h->T.mask + 1) {
+    if (cv_table_slots(capacity, 16) == (uint64_t)h->T.mask + 1) {
         h->capacity = capacity;
         return 0;
     }
     std::vector<uint32_t> mem;
     CvUniqTable to{};
-    carve(mem, slots_for(capacity), h->T.seed, &to);
+    carve(mem, capacity, h->T.seed, &to);
     uint32_t dstat[CVU_D_WORDS] = {};
     for (uint32_t s : lanes((size_t)h->T.mask + 1, order)) cvu_rehash(h->T, to, s, dstat);
     const int rc = fold(h, dstat);
@@ -110,7 +93,7 @@ int huq_commit(void *p, uint32_t ntx, const uint32_t *key, const uint32_t *begin
     if (ntx == 0) return 0;
     const uint32_t S = begin[ntx];
     if (h->resident + S > h->capacity) return -4;
-    std::vector<uint32_t> btab((size_t)bmask_for(S) + 1, CVU_NONE), rep(S + 1), res(S + 1), stx(S + 1), owner(S + 1), last(S + 1);
+    std::vector<uint32_t> btab((size_t)cv_table_slots(S, 16), CVU_NONE), rep(S + 1), res(S + 1), stx(S + 1), owner(S + 1), last(S + 1);
     std::vector<uint32_t> s0(ntx), s1(ntx), dstat(CVU_D_WORDS, 0);
     CvUniqBatch B{};
     B.ntx = ntx;
@@ -180,7 +163,7 @@ int huq_load(void *p, uint32_t n, const uint32_t *key, const uint32_t *id, uint3
     HSet *h = static_cast<HSet *>(p);
     if (n == 0) return 0;
     if (h->resident + n > h->capacity) return -4;
-    std::vector<uint32_t> btab((size_t)bmask_for(n) + 1, CVU_NONE), rep(n), res(n), dstat(CVU_D_WORDS, 0);
+    std::vector<uint32_t> btab((size_t)cv_table_slots(n, 16), CVU_NONE), rep(n), res(n), dstat(CVU_D_WORDS, 0);
     CvUniqBatch B{};
     B.nstates = n;
     B.key = key;

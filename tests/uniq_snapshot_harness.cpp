@@ -127,7 +127,7 @@ int hus_install(void *p, uint64_t n, const uint32_t *key, const uint32_t *id, ui
     if (n > (1ull << 30)) return -5;
     HSet fresh;
     fresh.capacity = h->capacity > n ? h->capacity : (size_t)n;
-    carve(fresh.mem, slots_for(fresh.capacity), seed, &fresh.T);
+    carve(fresh.mem, fresh.capacity, seed, &fresh.T);
     const int rc = huq_load(&fresh, (uint32_t)n, key, id, index, caller, order);
     if (rc) return rc;                            // the old table is untouched
     h->mem.swap(fresh.mem);
